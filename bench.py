@@ -7,6 +7,7 @@ A "step" is one generator forward over one resident batch of synthetic mels (inp
 Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline` and `cpu_baseline` objects.
 
     python bench.py                       # N=1
+    python bench.py --dump-outputs bench_outputs   # also write the last timed step's outputs as bench_outputs/<name>.npy (compare two builds output for output)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -119,6 +120,43 @@ def measured_mfma_insts():
         return tot / 3.0 if tot else None
     except Exception:
         return None
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all arrays of one dump together
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """`--dump-outputs DIR`: write what the timed path returned in its last step as DIR/<name>.npy, floating arrays as float32 (float64 stays
+    float64), integers as float64.  When the arrays together exceed `budget` bytes, each one is replaced by the same fraction of its elements at
+    fixed positions (numpy Generator seeded with `seed`, flat indices in ascending order, written beside it as DIR/<name>.index.npy in float64),
+    so runs with the same arguments dump the same positions.  Returns {name: {'shape', 'dtype', 'sampled'}} for the result line."""
+    import numpy as np
+    import torch
+    flat = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            a = (a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()).cpu().numpy()
+        else:
+            a = np.asarray(a)
+            a = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+        flat[name] = a
+    total = sum(a.nbytes for a in flat.values())
+    frac = 1.0
+    if total > budget:
+        frac = budget / float(sum(a.size * (a.itemsize + 8) for a in flat.values()))   # sample + its float64 index
+    os.makedirs(outdir, exist_ok=True)
+    info = {}
+    for name, a in flat.items():
+        sampled = frac < 1.0
+        if sampled:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, int(a.size * frac), replace=False))
+            np.save(os.path.join(outdir, name + '.index.npy'), idx.astype(np.float64))
+            np.save(os.path.join(outdir, name + '.npy'), a.reshape(-1)[idx])
+        else:
+            np.save(os.path.join(outdir, name + '.npy'), a)
+        info[name] = {'shape': list(a.shape), 'dtype': str(a.dtype), 'sampled': sampled}
+    return info
 
 
 def self_check(g, mel, out, h, sd, tol=1e-4):
@@ -405,6 +443,7 @@ def bench_train(args):
         out = T.cubegan_training_step(model, batch, opts, reducers, rng=crop)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, {k: float(v) for k, v in out.items()}) if args.dump_outputs and rank == 0 else None
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
@@ -459,6 +498,8 @@ def bench_train(args):
                                      'MPD / MSD discriminators: all convolution launches of one step',
                            'flops_per_step': fl, 'flops_model': 'bench.py::cubegan_step_conv_flops (3 x generator forward + 9 x discriminator forward over b sequences)',
                            'note': 'whole-step time in the denominator (LSTM recurrences, losses, optimizers, exchange included): a lower bound on the convolution kernels\' own fraction'}
+        if dumped is not None:
+            res['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         print(json.dumps(res))
     dist.barrier()
     dist.destroy_process_group()
@@ -610,6 +651,10 @@ def bench_e2e(args):
         elapsed = time.perf_counter() - t0
         assert nsamp_p == nsamp and all(bool(torch.equal(outs_p[i][0], outs[i][0])) for i in outs), 'pipelined synthesis differs from the sequential one'
         outs = outs_p
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {'waveform': torch.cat([outs[i][0].reshape(-1) for i in sorted(outs)]),
+                                                  'lengths': np.array([int(outs[i][1]) for i in sorted(outs)], dtype=np.float64)})
     # per-phase device time of one more (untimed) pass
     tm = []
     run(tm)
@@ -660,7 +705,7 @@ def bench_e2e(args):
                                          'generator_phase_frac': (fl_gen[1] / (phases['generator'] * 1e-3) / 1e12 / (2500.0 / 3)) if phases.get('generator') else None,
                                          'note': 'rank 0\'s shard over rank 0\'s wall time; generator_phase_frac = generator FLOPs over the generator phase\'s device time'})(
                 e2e_flops(float(nsamp) / 240.0, float(sum(int(lens[i]) for i in mine)))),
-            'cpu_baseline': None}))
+            'cpu_baseline': None, **({'dump_outputs': {'dir': args.dump_outputs, 'arrays': dumped}} if dumped is not None else {})}))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -686,7 +731,14 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='skip the secondary legs (fp32, B=1, WaveRNN)')
     ap.add_argument('--no-live-traffic', action='store_true', help='keep roofline.traffic from the committed PMC summary instead of measuring it with two rocprofv3 --pmc child passes (N = 1, default run only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy: the waveforms (infer: [batch, 1, samples]; '
+                         'e2e: the shard\'s sentences concatenated in sentence order, with their lengths) or the step\'s losses (train); at most 64 MB in all, '
+                         'beyond that a fixed seeded sample of every array (see bench.py::dump_outputs).  Inputs and weights are seeded: the same arguments give '
+                         'the same inputs on every run')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, torch.distributed.run, rendezvous on
         # 127.0.0.1 — the container hostname may not resolve) and hand their exit code back.  Under a launcher WORLD_SIZE is set and this is skipped.
@@ -755,6 +807,7 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)  # HIP events on the stream the kernels run on (torch current stream)
+    dumped = dump_outputs(args.dump_outputs, {'waveform': out}) if args.dump_outputs and rank == 0 else None
     assert bool(torch.isfinite(out).all())
     check_rms = self_check(g, mel, out, h, sd) if rank == 0 else None   # never report a time for wrong results
 
@@ -810,6 +863,8 @@ def main():
                                                     'source': os.path.relpath(PMC_CSV, ROOT) + ' (SQ_INSTS_MFMA, builder-run rocprofv3 pass, NOT measured in this run)'}},
         }
         res['self_check_rms_vs_oracle'] = check_rms
+        if dumped is not None:
+            res['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if precision == 'f16x3':
             # What the matrix pipe of THIS device sustains, measured now (csrc/probe.hip: register-only v_mfma_f32_32x32x16_f16 loop on every CU):
             # MI355X clocks to its power budget, so operands with real bit patterns run well below the nominal peak that `peak` must quote.

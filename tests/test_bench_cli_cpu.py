@@ -106,3 +106,29 @@ def test_live_traffic_reads_the_counter_databases(monkeypatch, tmp_path):
     fail['on'] = 'WRITE_SIZE'
     got, why = bench.live_traffic('f16x3', B, T)
     assert got is None and 'WRITE_SIZE' in why
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_beyond_the_budget(tmp_path):
+    """bench.py::dump_outputs (--dump-outputs DIR): arrays within the budget are written whole (float32, float64 kept, integers as float64);
+    beyond it every array keeps the same fraction of its elements at seeded positions, the dump stays within the budget and two dumps of
+    the same arrays are identical."""
+    import numpy as np
+    import torch
+    import bench
+    wav = torch.randn(3, 1, 1000, generator=torch.Generator().manual_seed(5))
+    lens = np.array([1000, 998, 7])
+    info = bench.dump_outputs(str(tmp_path / 'a'), {'waveform': wav, 'lengths': lens, 'loss': 0.25})
+    w = np.load(tmp_path / 'a' / 'waveform.npy')
+    assert w.dtype == np.float32 and np.array_equal(w, wav.numpy())
+    assert np.load(tmp_path / 'a' / 'lengths.npy').dtype == np.float64 and np.load(tmp_path / 'a' / 'loss.npy') == 0.25
+    assert not any(v['sampled'] for v in info.values()) and not (tmp_path / 'a' / 'waveform.index.npy').exists()
+    budget = 4096
+    for d in ('b', 'c'):
+        info = bench.dump_outputs(str(tmp_path / d), {'waveform': wav, 'lengths': lens}, budget=budget)
+        assert info['waveform']['sampled'] and info['waveform']['shape'] == [3, 1, 1000]
+    size = sum(os.path.getsize(p) - 128 for p in (tmp_path / 'b').iterdir())     # (np.save header: 128 bytes)
+    assert 0 < size <= budget
+    idx = np.load(tmp_path / 'b' / 'waveform.index.npy').astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(np.load(tmp_path / 'b' / 'waveform.npy'), wav.numpy().reshape(-1)[idx])
+    for name in ('waveform.npy', 'waveform.index.npy', 'lengths.npy', 'lengths.index.npy'):
+        assert np.array_equal(np.load(tmp_path / 'b' / name), np.load(tmp_path / 'c' / name))

@@ -23,7 +23,12 @@ def test_losses_and_codecs_match_reference_known_answers(golden_dir):
     assert _rel(m.loss(lg, y), z['mulaw_loss']) < 2e-6 and _rel(r.loss(lg, y), z['raw_loss']) < 2e-6
     assert np.array_equal(m.encode(y).numpy(), z['mulaw_enc']) and np.array_equal(m.encode(z['y']), z['mulaw_enc_np'])
     codes = np.arange(256)
-    assert np.array_equal(m.decode(torch.from_numpy(codes)).numpy(), z['mulaw_dec'])
+    # torch.exp on the CPU runs MKL's vector math, whose last bits depend on the host's instruction set: the known answer comes from an
+    # AVX-512 host, MKL's AVX2 / SSE4.2 paths (and the one it takes on AMD hosts) land up to 4 float32 ulp away from it
+    dec = m.decode(torch.from_numpy(codes)).numpy()
+    ulp = np.abs(dec.view(np.int32).astype(np.int64) - z['mulaw_dec'].view(np.int32).astype(np.int64))
+    assert dec.dtype == np.float32 and np.array_equal(np.sign(dec), np.sign(z['mulaw_dec'])) and ulp.max() <= 4
+    assert dec[0] == -1.0 and dec[255] == 1.0 and np.all(np.diff(dec) > 0)
     assert np.array_equal(m.decode(codes.astype(np.float64)), z['mulaw_dec_np'])
     assert np.array_equal(r.encode(y).numpy(), z['raw_enc']) and np.array_equal(r.decode(torch.from_numpy(codes).float()).numpy(), z['raw_dec'])
     for name, cls in (('mol', PL.MOLOutput), ('gm', PL.GaussianOutput), ('beta', PL.BetaOutput), ('mulaw', PL.MULAWOutput), ('raw', PL.RAWOutput)):
