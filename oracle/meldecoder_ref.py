@@ -54,8 +54,8 @@ def lstm_dir(x, w_ih, w_hh, b_ih, b_hh, reverse=False, hx=None):
     """One direction of one LSTM layer (torch gate order i,f,g,o).  x [B,T,I] -> y [B,T,H], (h,c)."""
     B, T, _ = x.shape
     H = w_hh.shape[1]
-    h = torch.zeros(B, H) if hx is None else hx[0]
-    c = torch.zeros(B, H) if hx is None else hx[1]
+    h = torch.zeros(B, H, dtype=x.dtype) if hx is None else hx[0]
+    c = torch.zeros(B, H, dtype=x.dtype) if hx is None else hx[1]
     ys = [None] * T
     xg = x @ w_ih.t() + b_ih
     order = range(T - 1, -1, -1) if reverse else range(T)
@@ -230,26 +230,46 @@ def textcoder_text_stack(sd, x_char, x_speaker):
     return h, linear(hd, sd, '_dur_output')
 
 
-def textcoder_inference(sd, x_char, x_speaker, masks, pframes=3):
-    """textcoder.py:140-189.  masks: float {0,1} [steps, 2, 1, 256] PreNet dropout masks (one pair per AR step)."""
+def textcoder_overlay(sd, x_char, x_speaker, pframes=3):
+    """textcoder.py:140-171: text stack, durations, expansion, overlay BiLSTM -> (overlay states [1, S, 1024], durations)."""
     h, out_dur = textcoder_text_stack(sd, x_char, x_speaker)
     durs = torch.argmax(out_dur, dim=-1).reshape(-1).tolist()
     f2p = durations_to_frame2phone(durs)
     h = expand_pframes(h, [f2p], pframes)
     h, _ = lstm(h, sd, '_rnn_overlay', 2, True)
-    last = torch.ones(1, 1, 80) * -5
+    return h, durs
+
+
+def textcoder_inference(sd, x_char, x_speaker, masks, pframes=3):
+    """textcoder.py:140-189.  masks: float {0,1} [steps, 2, 1, 256] PreNet dropout masks (one pair per AR step)."""
+    h, durs = textcoder_overlay(sd, x_char, x_speaker, pframes)
+    if h.shape[1] == 0:
+        return torch.zeros(1, 0, 80), durs
+    mel = textcoder_ar_decode(sd, h, masks, pframes=pframes)
+    return mel + postnet(mel, sd), durs
+
+
+def textcoder_ar_decode(sd, h_overlay, masks, steps=None, pframes=3):
+    """The AR loop of textcoder.py:174-185 over a batch: h_overlay [B, S, 1024] overlay-BiLSTM states, masks [S, 2, B, 256] {0,1}
+    PreNet dropout masks, steps [B] valid steps per utterance (None: all S).  Computes in the dtype of h_overlay (the state dict
+    and the masks must match it).  -> pre-postnet mel [B, S * pframes, 80], rows past an utterance's steps zero."""
+    B, S, _ = h_overlay.shape
+    last = torch.full((B, 1, 80), -5.0, dtype=h_overlay.dtype)
     hx = None
     outs = []
-    for t in range(h.shape[1]):
-        pn = prenet(last, sd, masks[t])
-        y, hx = lstm(torch.cat([h[:, t:t + 1], pn], dim=-1), sd, '_mel_rnn', 2, False, hx=hx)
+    for t in range(S):
+        pn = prenet(last, sd, masks[t].reshape(2, B, 1, -1))
+        y, hx = lstm(torch.cat([h_overlay[:, t:t + 1], pn], dim=-1), sd, '_mel_rnn', 2, False, hx=hx)
         o = linear(y, sd, '_mel_output')
         outs.append(o)
         last = o[:, :, -80:]
     if not outs:
-        return torch.zeros(1, 0, 80), durs
-    mel = torch.cat(outs, dim=1).reshape(1, -1, 80)
-    return mel + postnet(mel, sd), durs
+        return torch.zeros(B, 0, 80, dtype=h_overlay.dtype)
+    y = torch.cat(outs, dim=1)                                       # [B, S, 80 * pframes]
+    if steps is not None:
+        for b, n in enumerate(steps):
+            y[b, int(n):] = 0
+    return y.reshape(B, S * pframes, 80)
 
 
 def textcoder_forward(sd, x_char, x_speaker, frame2phone, y_mgc, masks, pframes=3):

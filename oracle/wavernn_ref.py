@@ -2,6 +2,7 @@
 µ-law codec (cube/networks/loss.py:236-269) and of CubenetVocoder's chunk fold/unfold (vocoder.py:109-131).
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -197,3 +198,14 @@ def synthetic_inputs(B, T, seed=1234, upsample=240, upsample_low=10, n_mel=80):
     mel = np.clip(rng.randn(B, T, n_mel) - 2.0, -5.0, 1.0).astype(np.float32)
     x_low = rng.uniform(-1, 1, size=(B, T * upsample // upsample_low)).astype(np.float32)
     return mel, x_low
+
+
+def gumbel_from_seed(noise_seed, B, L, S=256):
+    """Injected Gumbel noise of the long goldens (too large to store): legacy RandomState uniforms in float64, the Gumbel
+    transform -log(-log(u)) in float64, one cast to float32.  [B, L, S]"""
+    u = np.random.RandomState(noise_seed).uniform(size=(B, L, S))
+    return (-np.log(-np.log(u))).astype(np.float32)
+
+
+def noise_sha256(g):
+    return hashlib.sha256(np.ascontiguousarray(g, dtype=np.float32).tobytes()).hexdigest()

@@ -42,6 +42,48 @@ def test_textcoder_inference_and_forward_match_reference(golden_dir):
     assert float((o_post - torch.from_numpy(z['tf_post'])).pow(2).mean().sqrt()) < 1e-5
 
 
+def textcoder_pipeline_bound(sd, X, masks, pframes, S):
+    """Per-step bound for an fp32 run of the whole Textcoder inference (text stack, overlay BiLSTM, AR loop) against another:
+    4 x the largest deviation of the oracle in float32 from the oracle in float64 up to that step + 1e-6.  [S]"""
+    ys = []
+    for dt in (torch.float32, torch.float64):
+        sdd = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in sd.items()}
+        with torch.no_grad():
+            h, _ = M.textcoder_overlay(sdd, X['x_char'], X['x_speaker'], pframes)
+            assert h.shape[1] == S, 'float32 and float64 runs chose different durations'
+            ys.append(M.textcoder_ar_decode(sdd, h, masks.to(dt), pframes=pframes).reshape(1, S, -1).double().numpy())
+    return 4.0 * np.maximum.accumulate(np.abs(ys[0] - ys[1]).max(axis=(0, 2))) + 1e-6
+
+
+@pytest.mark.parametrize('name', ['textcoder_long', 'textcoder_pf1'])
+def test_textcoder_long_ar_run_matches_reference(golden_dir, name):
+    """105 AR steps of three frames / 300 steps of one frame (pframes=1, O = 80), the reference's own run with its dropout masks replayed:
+    every AR step's `_mel_output` row within the fp32 bound of textcoder_pipeline_bound, the post-net mel and the teacher-forced
+    outputs within the bars of textcoder_a."""
+    z, sd = _load(golden_dir, name)
+    pf = int(z['pframes'])
+    X = {'x_char': torch.from_numpy(z['x_char']), 'x_speaker': torch.from_numpy(z['x_speaker'])}
+    mk = torch.from_numpy(z['masks']).unsqueeze(2)
+    ref = z['mel_ar'].astype(np.float64)
+    S = ref.shape[1]
+    assert S >= (100 if pf == 3 else 300)
+    with torch.no_grad():
+        h, _ = M.textcoder_overlay(sd, X['x_char'], X['x_speaker'], pf)
+        y = M.textcoder_ar_decode(sd, h, mk, pframes=pf).reshape(1, S, -1).double().numpy()
+        mel, _ = M.textcoder_inference(sd, X['x_char'], X['x_speaker'], mk, pframes=pf)
+        ntf = int(z['tf_nph'])                  # the teacher-forced forward ran on the first tf_nph phonemes
+        o_dur, o_mel, o_post = M.textcoder_forward(sd, X['x_char'][:, :ntf], X['x_speaker'], [list(z['f2p_tf'])], torch.from_numpy(z['y_mgc']),
+                                                   torch.from_numpy(z['masks_tf']), pframes=pf)
+    bound = textcoder_pipeline_bound(sd, X, mk, pf, S)
+    err = np.abs(y - ref).max(axis=(0, 2))
+    bad = np.flatnonzero(err > bound)
+    assert not len(bad), 'step %d of %d: error %.3g > bound %.3g' % (bad[0], S, err[bad[0]], bound[bad[0]])
+    assert mel.shape == z['mel'].shape and float((mel - torch.from_numpy(z['mel'])).pow(2).mean().sqrt()) < 1e-5
+    assert float((o_dur - torch.from_numpy(z['tf_dur'])).abs().max()) < 1e-4
+    assert float((o_mel - torch.from_numpy(z['tf_mel'])).pow(2).mean().sqrt()) < 1e-5
+    assert float((o_post - torch.from_numpy(z['tf_post'])).pow(2).mean().sqrt()) < 1e-5
+
+
 def test_lstm_restatement_matches_torch_lstm():
     torch.manual_seed(0)
     m = torch.nn.LSTM(input_size=20, hidden_size=16, num_layers=2, bidirectional=True, batch_first=True)

@@ -1,5 +1,6 @@
 """Oracle pinning (CPU): the C WaveRNN restatement vs vectors produced by the reference itself
 (tools/gen_golden_wavernn.py imports /root/reference and replays torch's real sampler noise)."""
+import functools
 import os
 
 import numpy as np
@@ -182,3 +183,67 @@ def test_vocoder_training_step_restatement_matches_reference(golden_dir, name):
         ref = torch.from_numpy(z['p%d/%s' % (steps - 1, k)])
         # one Adam step moves a weight by ~lr = 1e-3: the update itself is held to 1 %
         assert float((sd2[k] - ref).abs().max()) < 2e-5, (k, float((sd2[k] - ref).abs().max()))
+
+
+# ---- long horizon: 24 000 steps at H = 512, noise generated from a stored seed (tools/gen_golden_wavernn.py run_case_long) ---------
+LONG = ['wavernn_hr_h512_n1_long', 'wavernn_hr_h512_n2_long']
+
+
+def long_noise(z):
+    """The fixture's sampler noise rebuilt from its noise_seed; fails if it is not the noise the reference ran on."""
+    L = int(z['T']) * 240
+    g = O.gumbel_from_seed(int(z['noise_seed']), int(z['B']), L)
+    got = O.noise_sha256(g)
+    assert got == str(z['noise_sha256']), ('Gumbel noise rebuilt from noise_seed %d has sha256 %s, the fixture was made with %s: '
+                                           'numpy\'s RandomState stream or float64 log changed' % (int(z['noise_seed']), got, str(z['noise_sha256'])))
+    return g
+
+
+def first_divergence(idx, z):
+    """-> (first step whose sampled index differs from the reference's, or L; message naming it and its margin)"""
+    diff = np.flatnonzero((idx != z['idx']).any(axis=0))
+    s = int(diff[0]) if len(diff) else idx.shape[1]
+    t_tie = int(z['t_tie'])
+    msg = 'first index differing from the reference at step %d (t_tie %d): margin there %.3g (delta %g)' % (
+        s, t_tie, float(z['margin'][:, s].min()) if s < idx.shape[1] else np.inf, float(z['delta']))
+    return s, msg
+
+
+def check_against_long_reference(z, idx, wav, logits):
+    """idx / wav bit-exact before t_tie; the free-running logits the reference stored every log_every steps within 1e-4 up to the first
+    divergence (past it the two runs condition on different histories)."""
+    t_tie = int(z['t_tie'])
+    s, msg = first_divergence(idx, z)
+    assert s >= t_tie, msg
+    assert np.array_equal(wav[:, :t_tie], z['wav'][:, :t_tie]), msg
+    every = int(z['log_every'])
+    k = min(z['logits_fr'].shape[1], s // every + 1)
+    err = np.abs(logits[:, ::every][:, :k] - z['logits_fr'][:, :k]).max(axis=(0, 2))
+    assert float(err.max()) <= 1e-4, 'free-running logits at step %d differ by %.3g (%s)' % (int(err.argmax()) * every, float(err.max()), msg)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def long_oracle(golden_dir, name):
+    z = np.load(os.path.join(golden_dir, name + '.npz'))
+    _, sd, kw = _case(golden_dir, name)
+    return O.decode(sd, z['mel'], z['x_low'], mode=O.MODE_NOISE, noise=long_noise(z), want_logits=True, **kw)
+
+
+@pytest.mark.parametrize('name', LONG)
+def test_long_run_follows_reference(golden_dir, name):
+    """24 000 autoregressive steps: the oracle samples the reference's indices at every step before t_tie, the first step where the
+    reference's top-two margin of log_softmax + g falls below delta (an fp32 summation-order difference may break such a near tie
+    either way), and its logits follow the reference's to 1e-4."""
+    z = np.load(os.path.join(golden_dir, name + '.npz'))
+    assert int(z['t_tie']) >= 4800 and z['idx'].shape == (1, 24000)
+    idx, wav, logits = long_oracle(golden_dir, name)
+    check_against_long_reference(z, idx, wav, logits)
+
+
+@pytest.mark.parametrize('name', LONG)
+def test_long_case_teacher_forced_prefix(golden_dir, name):
+    z, sd, kw = _case(golden_dir, name)
+    T = int(z['T_tf'])
+    _, _, logits = O.decode(sd, z['mel'][:, :T], z['x_low'][:, :T * 24], mode=O.MODE_ARGMAX, forced_x=z['audio'], want_logits=True, **kw)
+    assert float(np.abs(logits - z['logits_tf']).max()) < 1e-4

@@ -257,3 +257,32 @@ def test_default_kernel_choice_by_batch(monkeypatch):
     monkeypatch.setenv('TTSC_WR_TILE2', '0')
     idx, _, _ = net2.decode(X, mode='philox', seed=3)
     assert net2.last_kernel == 'stream' and np.array_equal(idx.cpu().numpy(), ridx)
+
+
+# ---- long horizon: 24 000 steps at H = 512 with the reference's run as the yardstick (tests/test_oracle_wavernn.py) -------------------
+@pytest.mark.parametrize('name', ['wavernn_hr_h512_n1_long', 'wavernn_hr_h512_n2_long'])
+def test_long_run_follows_reference_and_oracle(golden_dir, name, wr_kernel):
+    """100 frames (24 000 samples) of one utterance, the reference's noise injected: the kernel's indices equal the reference's at
+    every step before t_tie and its free-running logits follow the reference's to 1e-4 (the bars of the CPU oracle test); over the
+    WHOLE run, past t_tie too, indices, samples and logits are bit-exact with the C oracle (computed once for both kernel variants)."""
+    from tests.test_oracle_wavernn import check_against_long_reference, long_noise, long_oracle
+    z = np.load(os.path.join(golden_dir, name + '.npz'))
+    H, N = int(z['H']), int(z['N'])
+    sd = O.synthetic_state_dict(H=H, num_layers=N, use_lowres=True, seed=int(z['seed']))
+    net = _net(H, N, True, sd)
+    X = {'mel': torch.from_numpy(z['mel']), 'x_low': torch.from_numpy(z['x_low'])}
+    idx, wav, logits = net.decode(X, mode='noise', noise=long_noise(z), want_logits=True)
+    assert net.last_kernel == ('tile' if wr_kernel == 'tile' else 'stream')
+    idx, wav, logits = idx.cpu().numpy(), wav.cpu().numpy(), logits.cpu().numpy()
+    check_against_long_reference(z, idx, wav, logits)
+    ridx, rwav, rlog = long_oracle(golden_dir, name)
+    bad = np.argwhere(idx != ridx)
+    assert not len(bad), 'first index mismatch with the oracle at step %d' % bad[0, 1]
+    assert np.array_equal(wav, rwav)
+    bad = np.argwhere(logits != rlog)
+    assert not len(bad), 'first logit mismatch with the oracle at step %d' % bad[0, 1]
+    # teacher-forced prefix vs the reference's _train_forward
+    T = int(z['T_tf'])
+    xin = np.concatenate([np.zeros_like(z['audio'][:, :1]), z['audio'][:, :-1]], axis=1)
+    Xt = {'mel': X['mel'][:, :T], 'x_low': X['x_low'][:, :T * 24], 'x': torch.from_numpy(xin).cuda()}
+    assert float(np.abs(net(Xt).cpu().numpy() - z['logits_tf']).max()) < 1e-4

@@ -1,6 +1,6 @@
 """Golden vectors for the mel decoders, produced by the REFERENCE ITSELF (imported from /root/reference).
 
-    python tools/gen_golden_meldecoder.py  ->  tests/golden/languasito2_*.npz, textcoder_*.npz
+    python tools/gen_golden_meldecoder.py [case ...]  ->  tests/golden/languasito2_*.npz, textcoder_*.npz
 
 Weights: oracle.meldecoder_ref.fill_state_dict(named_shapes(reference module), seed) loaded with strict=True — the
 fixture stores only the seed and the (name, shape) list, the tests rebuild identical tensors.  The only stochastic
@@ -54,17 +54,19 @@ class Enc:
         self.max_duration = max_duration
 
 
-def gen_textcoder(name, seed, nph, max_duration=9):
+def gen_textcoder(name, seed, nph, max_duration=9, pframes=3, n_masks=400, keep_ar=False, tf_nph=None):
+    """keep_ar: also store the reference's per-step `_mel_output` rows (pre-postnet) as mel_ar [1, steps, 80 * pframes] (and tf_nph).
+    tf_nph: the teacher-forced forward runs on the first tf_nph phonemes only (None: all; keeps long fixtures small)."""
     torch.manual_seed(0)
     enc = Enc(40, 2, 200, max_duration)
-    net = CubenetTextcoder(enc)
+    net = CubenetTextcoder(enc, pframes=pframes)
     shapes = M.named_shapes(net)
     net.load_state_dict(M.fill_state_dict(shapes, seed), strict=True)
     net.eval()
     rng = np.random.RandomState(seed)
     x_char = torch.from_numpy(rng.randint(1, 41, size=(1, nph))).long()
     x_speaker = torch.tensor([[1]]).long()
-    masks = torch.from_numpy((rng.uniform(size=(400, 2, 1, 1, 256)) > 0.5).astype(np.float32))
+    masks = torch.from_numpy((rng.uniform(size=(n_masks, 2, 1, 1, 256)) > 0.5).astype(np.float32))
     calls = [0]
     orig = torch.dropout
 
@@ -74,17 +76,23 @@ def gen_textcoder(name, seed, nph, max_duration=9):
         calls[0] += 1
         return x * m * 2.0
 
+    ar_rows = []
+    hook = net._mel_output.register_forward_hook(lambda mod, inp, out: ar_rows.append(out.detach().clone()))
     torch.dropout = replay
     try:
         with torch.no_grad():
             mel = net.inference({'x_char': x_char, 'x_speaker': x_speaker})
+        hook.remove()
         steps = calls[0] // 2
+        assert steps < n_masks and len(ar_rows) == steps
         # teacher-forced forward on the same text with a synthetic alignment / target mel
-        durs_tf = rng.randint(1, 7, size=nph)
+        tf_nph = nph if tf_nph is None else tf_nph
+        x_tf = x_char[:, :tf_nph]
+        durs_tf = rng.randint(1, 7, size=tf_nph)
         f2p = [p for p, d in enumerate(durs_tf) for _ in range(d)]
         F_ = len(f2p)
         y_mgc = torch.from_numpy(np.clip(rng.randn(1, F_, 80) - 2, -5, 1).astype(np.float32))
-        n_tf = F_ // 3 + 1
+        n_tf = F_ // pframes + 1
         masks_tf = torch.from_numpy((rng.uniform(size=(2, 1, n_tf, 256)) > 0.5).astype(np.float32))
         calls[0] = 0
 
@@ -95,19 +103,31 @@ def gen_textcoder(name, seed, nph, max_duration=9):
 
         torch.dropout = replay_tf
         with torch.no_grad():
-            o_dur, o_pitch, o_mel, o_post = net.forward({'x_char': x_char, 'x_speaker': x_speaker, 'y_frame2phone': [f2p],
+            o_dur, o_pitch, o_mel, o_post = net.forward({'x_char': x_tf, 'x_speaker': x_speaker, 'y_frame2phone': [f2p],
                                                          'y_mgc': y_mgc})
     finally:
         torch.dropout = orig
+    extra = dict(pframes=pframes, mel_ar=torch.cat(ar_rows, dim=1).numpy(), tf_nph=tf_nph) if keep_ar else {}
     np.savez_compressed(os.path.join(OUT, name + '.npz'), seed=seed, shapes=json.dumps(shapes), x_char=x_char.numpy(),
                         x_speaker=x_speaker.numpy(), masks=masks[:steps, :, 0].numpy(), mel=mel.numpy(),
                         f2p_tf=np.asarray(f2p), y_mgc=y_mgc.numpy(), masks_tf=masks_tf.numpy(), tf_dur=o_dur.numpy(),
-                        tf_mel=o_mel.numpy(), tf_post=o_post.numpy(), max_duration=max_duration)
+                        tf_mel=o_mel.numpy(), tf_post=o_post.numpy(), max_duration=max_duration, **extra)
     print(name, 'AR steps', steps, 'mel', tuple(mel.shape), 'rms', float(mel.pow(2).mean().sqrt()), 'tf mel', tuple(o_mel.shape))
 
 
+NPH_LONG, NPH_PF1 = 270, 50
+
+CASES = {
+    'languasito2_a': lambda: gen_languasito('languasito2_a', 31, 17),
+    'languasito2_b': lambda: gen_languasito('languasito2_b', 32, 5),
+    'textcoder_a': lambda: gen_textcoder('textcoder_a', 41, 11),
+    # long AR runs: ~100 steps of three frames, and one frame per step (pframes=1, O = 80)
+    'textcoder_long': lambda: gen_textcoder('textcoder_long', 42, NPH_LONG, n_masks=1024, keep_ar=True, tf_nph=40),
+    'textcoder_pf1': lambda: gen_textcoder('textcoder_pf1', 43, NPH_PF1, pframes=1, n_masks=1024, keep_ar=True, tf_nph=NPH_PF1),
+}
+
 if __name__ == '__main__':
+    # python tools/gen_golden_meldecoder.py [case ...]   (no argument: every case)
     os.makedirs(OUT, exist_ok=True)
-    gen_languasito('languasito2_a', 31, 17)
-    gen_languasito('languasito2_b', 32, 5)
-    gen_textcoder('textcoder_a', 41, 11)
+    for c in sys.argv[1:] or list(CASES):
+        CASES[c]()

@@ -106,14 +106,17 @@ class CubenetTextcoder(nn.Module):
         self._hip['_melar_sig'] = sig
         return hnd
 
-    def _ar_decode(self, h, dropout_masks=None, steps=None, seed=None):
-        """textcoder.py:174-185 as ONE persistent kernel launch (csrc/melar.hip).  h: overlay states [B, S, 1024]."""
+    def _ar_decode(self, h, dropout_masks=None, steps=None, seed=None, out=None):
+        """textcoder.py:174-185 as ONE persistent kernel launch (csrc/melar.hip).  h: overlay states [B, S, 1024]; dropout_masks
+        [S, 2, B, 256] or None (in-kernel Philox from seed); steps [B] or None (all S); out: optional device tensor [B, S, 80 * pframes]
+        the kernel writes (every element of it)."""
         hnd = self._melar_handle()
         B, S, _ = h.shape
         r = self._mel_rnn
         n_ov = r.weight_ih_l0.shape[1] - 256
         xg1 = linear_hip(h, r.weight_ih_l0[:, :n_ov].contiguous(), r.bias_ih_l0 + r.bias_hh_l0)    # hoisted input projection
-        y = torch.empty((B, S, 80 * self._pframes), dtype=torch.float32, device=h.device)
+        y = torch.empty((B, S, 80 * self._pframes), dtype=torch.float32, device=h.device) if out is None else out
+        assert y.shape == (B, S, 80 * self._pframes) and y.dtype == torch.float32 and y.is_contiguous() and y.device == h.device
         m = None
         if dropout_masks is not None:
             m = torch.as_tensor(dropout_masks).to(h.device).float().reshape(S, 2, B, 256).permute(2, 0, 1, 3).contiguous()
