@@ -548,6 +548,20 @@ int ttsc_lstm_seq_forward_train(const float* xg_dev, const float* whh_packed_dev
 int ttsc_lstm_seq_backward(const float* dy_dev, const float* gates_dev, const float* c_dev, const float* whhT_packed_dev,
                            float* dgates_dev, const int32_t* lengths_dev, int32_t B, int32_t T, int32_t H, int32_t ndir,
                            int64_t ldy, int32_t yoff, void* stream);
+/* Which kernels ttsc_lstm_seq_forward_train (backward = 0) or ttsc_lstm_seq_backward (backward = 1) launch for a batch of B utterances, ndir
+ * directions and hidden size H on the CURRENT device (lengths = NULL); the launchers call the same selection.  Returns a path id, < 0 for a bad shape,
+ * and fills info[3] = {G members per (utterance, direction), NB utterances per member group (SPLIT_RES_NB) or per workgroup (SEQ), launches}:
+ *   TTSC_LSTM_PATH_SEQ           lstm_seq_kernel<NB> / lstm_bwd_kernel            one workgroup per (utterance tile, direction), rows streamed
+ *   TTSC_LSTM_PATH_SPLIT         lstm_seq_split_kernel / lstm_bwd_split_kernel    G workgroups per sequence, counter hand-off
+ *   TTSC_LSTM_PATH_SPLIT_RES     lstm_seq_split_res_kernel / lstm_bwd_split_res_kernel   W_hh in registers over G members, granule hand-off
+ *   TTSC_LSTM_PATH_SPLIT_RES_NB  lstm_seq_split_res_nb_kernel<NB> (forward only)  the same member groups stepping NB utterances together
+ *   TTSC_LSTM_PATH_RESIDENT      lstm_seq_resident_kernel / lstm_bwd_resident_kernel   H = 64 / 128, one workgroup per sequence */
+#define TTSC_LSTM_PATH_SEQ 0
+#define TTSC_LSTM_PATH_SPLIT 1
+#define TTSC_LSTM_PATH_SPLIT_RES 2
+#define TTSC_LSTM_PATH_SPLIT_RES_NB 3
+#define TTSC_LSTM_PATH_RESIDENT 4
+int32_t ttsc_lstm_train_path(int32_t B, int32_t ndir, int32_t H, int32_t backward, int32_t* info);
 /* Training of the WaveRNN vocoder (`WaveRNN._train_forward` cube/networks/modules.py:505-539 + `training_step` 553-563: torch.nn.GRU
  * over the teacher-forced sequence, differentiated by torch autograd).  Gate order r,z,n; one layer, unidirectional:
  *   ttsc_gru_pack_whh_device  weight_hh [3H,H] (device) -> out_dev [3H*H]: forward (transpose=0) / backward (transpose=1) packing
@@ -564,6 +578,16 @@ int ttsc_gru_seq_forward(const float* xg_dev, const float* whh_packed_dev, const
                          const float* h0_dev, int32_t B, int32_t T, int32_t H, void* stream);
 int ttsc_gru_seq_backward(const float* dy_dev, const float* saved_dev, const float* y_dev, const float* h0_dev,
                           const float* whhT_packed_dev, float* dgi_dev, float* dgh_dev, int32_t B, int32_t T, int32_t H, void* stream);
+/* Which kernels ttsc_gru_seq_forward / ttsc_gru_seq_backward launch for B utterances of hidden size H on the CURRENT device (both directions of
+ * time take the same path; the launchers call the same selection).  Returns a path id, < 0 for a bad shape, and fills info[3] = {G members per
+ * utterance, 1, 1}:
+ *   TTSC_GRU_PATH_SEQ        gru_seq_kernel / gru_bwd_kernel                      one workgroup per utterance
+ *   TTSC_GRU_PATH_SPLIT      gru_seq_split_kernel / gru_bwd_split_kernel          G streaming members per utterance, counter hand-off
+ *   TTSC_GRU_PATH_SPLIT_RES  gru_seq_split_res_kernel / gru_bwd_split_res_kernel  W_hh in registers over G members, granule hand-off */
+#define TTSC_GRU_PATH_SEQ 0
+#define TTSC_GRU_PATH_SPLIT 1
+#define TTSC_GRU_PATH_SPLIT_RES 2
+int32_t ttsc_gru_train_path(int32_t B, int32_t H, int32_t backward, int32_t* info);
 /* frees a device buffer returned by a ttsc_*_pack_* function */
 void ttsc_device_free(void* p);
 

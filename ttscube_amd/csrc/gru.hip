@@ -606,6 +606,17 @@ static int gru_resident_members(int B, int H) {
     if (!G || (long)G * B > device_cus() || B > 4096) return 0;
     return G;
 }
+// The one place that picks the kernel of ttsc_gru_seq_forward / ttsc_gru_seq_backward (both take the same path for a shape); the launchers
+// and ttsc_gru_train_path call it, so the query cannot drift from the dispatch.  *G = members per utterance.
+static int gru_train_path(int B, int H, int* G) {
+    if (const int Gr = gru_resident_members(B, H)) {   // weights in registers, granule hand-off (H = 512: 16 members, H = 256: 4)
+        *G = Gr;
+        return TTSC_GRU_PATH_SPLIT_RES;
+    }
+    *G = gru_split_members(B, H);
+    return *G > 1 ? TTSC_GRU_PATH_SPLIT : TTSC_GRU_PATH_SEQ;
+}
+
 static HandoffArea* gru_ring_area(hipStream_t s, size_t ring_bytes) {
     HandoffArea* ar = handoff_area("gru", s, 4096, ring_bytes);
     if (!ar || ar->rearm(s) != hipSuccess) return nullptr;
@@ -615,6 +626,19 @@ static HandoffArea* gru_ring_area(hipStream_t s, size_t ring_bytes) {
 // 0 = every hand-off of the split GRU launches on this device since the last call completed; 1 = a bounded spin timed out (that
 // launch's results are invalid).  Synchronises the device; meant for tests and debugging.
 extern "C" int32_t ttsc_gru_split_status(void) { return handoff_status("gru"); }
+
+extern "C" int32_t ttsc_gru_train_path(int32_t B, int32_t H, int32_t backward, int32_t* info) {
+    (void)backward;   // forward and backward of a shape take the same path
+    TTSC_REQUIRE(B > 0 && H >= 4 && H <= 512 && H % 4 == 0, "ttsc_gru_train_path: bad shape B=%d H=%d", B, H);
+    int G = 1;
+    const int path = gru_train_path(B, H, &G);
+    if (info) {
+        info[0] = G;
+        info[1] = 1;
+        info[2] = 1;
+    }
+    return path;
+}
 
 extern "C" int ttsc_gru_pack_whh_device(const float* whh_dev, int32_t H, int32_t transpose, float* out_dev, void* stream) {
     TTSC_REQUIRE(whh_dev && out_dev, "ttsc_gru_pack_whh_device: null argument");
@@ -630,7 +654,10 @@ extern "C" int ttsc_gru_seq_forward(const float* xg_dev, const float* whh_packed
     TTSC_REQUIRE(xg_dev && whh_packed_dev && bhh_dev && y_dev, "ttsc_gru_seq_forward: null argument");
     TTSC_REQUIRE(B > 0 && T > 0 && H >= 4 && H <= 512 && H % 4 == 0, "ttsc_gru_seq_forward: bad shape B=%d T=%d H=%d", B, T, H);
     GruArgs a{xg_dev, whh_packed_dev, bhh_dev, y_dev, saved_dev, h0_dev, B, T, H};
-    if (const int Gr = gru_resident_members(B, H)) {   // weights in registers, granule hand-off (H = 512: 16 members, H = 256: 4)
+    int G = 1;
+    const int path = gru_train_path(B, H, &G);
+    if (path == TTSC_GRU_PATH_SPLIT_RES) {
+        const int Gr = G;
         HandoffArea* ar = gru_ring_area((hipStream_t)stream, (size_t)B * 2 * H * sizeof(gru_u64));
         TTSC_REQUIRE(ar, "ttsc_gru_seq_forward: cannot allocate the hand-off ring");
         TTSC_HIP_CHECK(hipMemsetAsync(ar->buf, 0, (size_t)B * 2 * H * sizeof(gru_u64), (hipStream_t)stream));
@@ -645,8 +672,7 @@ extern "C" int ttsc_gru_seq_forward(const float* xg_dev, const float* whh_packed
         hipLaunchKernelGGL(gru_seq_split_res_kernel<32>, dim3((unsigned)Gr, (unsigned)B), dim3(512), lds, (hipStream_t)stream, sa, reinterpret_cast<gru_u64*>(ar->buf));
         return gru_check_launch("gru_seq_split_res_kernel");
     }
-    const int G = gru_split_members(B, H);
-    if (G > 1) {
+    if (path == TTSC_GRU_PATH_SPLIT) {
         HandoffArea* ar = gru_area(B, (hipStream_t)stream);
         TTSC_REQUIRE(ar, "ttsc_gru_seq_forward: cannot allocate the hand-off counters");
         GruSplitArgs sa{};
@@ -669,7 +695,10 @@ extern "C" int ttsc_gru_seq_backward(const float* dy_dev, const float* saved_dev
     TTSC_REQUIRE(dy_dev && saved_dev && y_dev && whhT_packed_dev && dgi_dev && dgh_dev, "ttsc_gru_seq_backward: null argument");
     TTSC_REQUIRE(B > 0 && T > 0 && H >= 4 && H <= 512 && H % 4 == 0, "ttsc_gru_seq_backward: bad shape B=%d T=%d H=%d", B, T, H);
     GruBwdArgs a{dy_dev, saved_dev, y_dev, h0_dev, whhT_packed_dev, dgi_dev, dgh_dev, B, T, H};
-    if (const int Gr = gru_resident_members(B, H)) {
+    int G = 1;
+    const int path = gru_train_path(B, H, &G);
+    if (path == TTSC_GRU_PATH_SPLIT_RES) {
+        const int Gr = G;
         HandoffArea* ar = gru_ring_area((hipStream_t)stream, (size_t)B * 2 * 3 * H * sizeof(gru_u64));
         TTSC_REQUIRE(ar, "ttsc_gru_seq_backward: cannot allocate the hand-off ring");
         TTSC_HIP_CHECK(hipMemsetAsync(ar->buf, 0, (size_t)B * 2 * 3 * H * sizeof(gru_u64), (hipStream_t)stream));
@@ -684,8 +713,7 @@ extern "C" int ttsc_gru_seq_backward(const float* dy_dev, const float* saved_dev
         hipLaunchKernelGGL(gru_bwd_split_res_kernel<96>, dim3((unsigned)Gr, (unsigned)B), dim3(512), lds, (hipStream_t)stream, sa, reinterpret_cast<gru_u64*>(ar->buf));
         return gru_check_launch("gru_bwd_split_res_kernel");
     }
-    const int G = gru_split_members(B, H);
-    if (G > 1) {
+    if (path == TTSC_GRU_PATH_SPLIT) {
         HandoffArea* ar = gru_area(B, (hipStream_t)stream);
         TTSC_REQUIRE(ar, "ttsc_gru_seq_backward: cannot allocate the hand-off counters");
         GruSplitArgs sa{};

@@ -1156,6 +1156,76 @@ extern "C" int32_t ttsc_lstm_set_group_size(int32_t n) {
 
 
 
+// The one place that picks the kernels of lstm_forward_impl / ttsc_lstm_seq_backward; the launchers and ttsc_lstm_train_path call these, so the
+// query cannot drift from the dispatch.  G = members per (utterance, direction); NB = utterances per member group (split_res) or per workgroup
+// (lstm_seq_kernel<NB>); launches = consecutive launches of the split_res kernels, each of up to `cap` groups.
+struct LstmPath {
+    int id, G, NB, launches, cap;
+};
+
+static LstmPath lstm_fwd_path(int B, int ndir, int H, bool train) {
+    // The split changes the summation order with G, so a result is bit-reproducible only among launches that pick the same
+    // G: always the case up to 64 (utterance, direction) pairs per launch (G = 4), e.g. a padded batch of <= 32 sentences
+    // against the same sentences run alone (tests/test_lstm_gpu.py, tests/test_api_gpu.py); larger batches (G = 2 / 1)
+    // agree to ~1e-6 relative.  TTSC_LSTM_SPLIT_INFER=0 keeps inference on the single-workgroup kernel.
+    static const bool split_infer = !(getenv("TTSC_LSTM_SPLIT_INFER") && atoi(getenv("TTSC_LSTM_SPLIT_INFER")) == 0);
+    if (H == 64 || H == 128) return LstmPath{TTSC_LSTM_PATH_RESIDENT, 1, 1, 1, 0};   // W_hh resident in registers, one thread per gate row
+    static const bool resident = !(getenv("TTSC_LSTM_RESIDENT") && atoi(getenv("TTSC_LSTM_RESIDENT")) == 0);
+    if ((train || split_infer) && resident && (H == 256 || H == 512)) {
+        // H = 256 / 512: G = 4 / 16 members per (utterance, direction), each thread holding 128 weights of W_hh in registers
+        // (lstm_seq_split_res_kernel: 512 threads = HU units x KS k-slices of 32).  All members of a launch must be resident, so a
+        // launch takes cus / G pairs; up to three consecutive launches still beat the streaming kernels (H = 256: 3 us per step
+        // and layer per launch against 9.8), and every batch size up to 3 * cus / (2 G) sentences then sums in the same order as
+        // a sentence run alone.
+        const int cus = device_cus();
+        if (cus >= 4) {
+            const int Gm = H == 256 ? 4 : 16;
+            const int pairs = B * ndir, cap = cus / Gm;
+            // utterances per member group (lstm_seq_split_res_nb_kernel: per utterance the same arithmetic as NB = 1).  Default: the smallest of
+            // 1 / 2 / 4 that fits the batch into ONE launch (shortest step), else 4 and up to three launches.  ttsc_lstm_set_group_size(n) asks
+            // for n per group whenever the batch has that many: fewer CUs held for a somewhat longer step — what a caller wants who runs the
+            // recurrence beside a kernel that fills the chip (Cubegan.inference_pipelined).
+            const int pref = g_lstm_group_size.load(std::memory_order_relaxed);
+            int NB = 1;
+            if (pref > 0) {
+                while (NB * 2 <= pref && NB * 2 <= B) NB *= 2;
+                while (NB < 8 && ((B + NB - 1) / NB) * ndir > 3 * cap) NB *= 2;
+            } else {
+                while (NB < 4 && ((B + NB - 1) / NB) * ndir > cap) NB *= 2;
+            }
+            const int groups = ((B + NB - 1) / NB) * ndir;
+            if (cap >= 1 && groups <= 3 * cap && pairs <= 16384)
+                return LstmPath{NB == 1 ? TTSC_LSTM_PATH_SPLIT_RES : TTSC_LSTM_PATH_SPLIT_RES_NB, Gm, NB, (groups + cap - 1) / cap, cap};
+        }
+    }
+    const int G = (train || split_infer) ? lstm_split_members(B, ndir, H) : 1;
+    if (G > 1) return LstmPath{TTSC_LSTM_PATH_SPLIT, G, 1, 1, 0};
+    return LstmPath{TTSC_LSTM_PATH_SEQ, 1, B * ndir > 512 ? 2 : 1, 1, 0};
+}
+
+static LstmPath lstm_bwd_path(int B, int ndir, int H) {
+    static const bool bwd_resident = !(getenv("TTSC_LSTM_BWD_RESIDENT") && atoi(getenv("TTSC_LSTM_BWD_RESIDENT")) == 0);
+    const int G = lstm_split_members(B, ndir, H);
+    if (G > 1) {
+        const int KS = 512 / (H / G);
+        // H = 256 over 4 members: 128 rows of W_hh^T per thread stay in registers, granule hand-off
+        return LstmPath{bwd_resident && 4 * H / KS == 128 ? TTSC_LSTM_PATH_SPLIT_RES : TTSC_LSTM_PATH_SPLIT, G, 1, 1, 0};
+    }
+    if (bwd_resident && (H == 64 || H == 128)) return LstmPath{TTSC_LSTM_PATH_RESIDENT, 1, 1, 1, 0};   // the slice's column of W_hh^T in registers
+    return LstmPath{TTSC_LSTM_PATH_SEQ, 1, 1, 1, 0};
+}
+
+extern "C" int32_t ttsc_lstm_train_path(int32_t B, int32_t ndir, int32_t H, int32_t backward, int32_t* info) {
+    TTSC_REQUIRE(B > 0 && ndir >= 1 && ndir <= 2 && H >= 4 && H <= 512 && H % 4 == 0, "ttsc_lstm_train_path: bad shape B=%d ndir=%d H=%d", B, ndir, H);
+    const LstmPath p = backward ? lstm_bwd_path(B, ndir, H) : lstm_fwd_path(B, ndir, H, true);
+    if (info) {
+        info[0] = p.G;
+        info[1] = p.NB;
+        info[2] = p.launches;
+    }
+    return p.id;
+}
+
 static int lstm_forward_impl(const float* xg_dev, const float* whh_packed_dev, float* y_dev, const int32_t* lengths_dev,
                              int32_t B, int32_t T, int32_t H, int32_t ndir, int64_t ldy, int32_t yoff, const float* h0_dev,
                              const float* c0_dev, float* hn_dev, float* cn_dev, float* gates_dev, float* c_dev, void* stream);
@@ -1196,8 +1266,9 @@ extern "C" int ttsc_lstm_seq_backward(const float* dy_dev, const float* gates_de
     TTSC_REQUIRE(B > 0 && T > 0 && ndir >= 1 && ndir <= 2 && H >= 4 && H <= 512 && H % 4 == 0, "ttsc_lstm_seq_backward: bad shape B=%d T=%d H=%d ndir=%d", B, T, H, ndir);
     TTSC_REQUIRE(ldy >= (int64_t)yoff + (int64_t)ndir * H, "ttsc_lstm_seq_backward: ldy too small");
     LstmBwdArgs a{dy_dev, gates_dev, c_dev, whhT_packed_dev, dgates_dev, lengths_dev, B, T, H, ndir, (int)ldy, yoff};
-    const int G = lstm_split_members(B, ndir, H);
-    if (G > 1) {
+    const LstmPath path = lstm_bwd_path(B, ndir, H);
+    if (path.id == TTSC_LSTM_PATH_SPLIT || path.id == TTSC_LSTM_PATH_SPLIT_RES) {
+        const int G = path.G;
         TTSC_REQUIRE(B * ndir <= 8192, "ttsc_lstm_seq_backward: too many sequences for the split kernel");
         LstmSplitArgs sa{};
         sa.bw = a;
@@ -1205,8 +1276,7 @@ extern "C" int ttsc_lstm_seq_backward(const float* dy_dev, const float* gates_de
         sa.HU = H / G;
         sa.KS = 512 / sa.HU;
         const size_t lds = ((size_t)4 * H + (size_t)sa.KS * sa.HU) * sizeof(float);
-        static const bool bwd_resident = !(getenv("TTSC_LSTM_BWD_RESIDENT") && atoi(getenv("TTSC_LSTM_BWD_RESIDENT")) == 0);
-        if (bwd_resident && 4 * H / sa.KS == 128) {   // H = 256 over 4 members: 128 rows of W_hh^T per thread stay in registers, granule hand-off
+        if (path.id == TTSC_LSTM_PATH_SPLIT_RES) {   // H = 256 over 4 members: 128 rows of W_hh^T per thread stay in registers, granule hand-off
             const size_t ring_bytes = (size_t)B * ndir * 2 * 4 * H * sizeof(lstm_u64);
             HandoffArea* ar2 = lstm_area((hipStream_t)stream, ring_bytes, true);
             TTSC_REQUIRE(ar2, "ttsc_lstm_seq_backward: cannot allocate the hand-off ring");
@@ -1228,8 +1298,7 @@ extern "C" int ttsc_lstm_seq_backward(const float* dy_dev, const float* gates_de
         }
         return TTSC_OK;
     }
-    static const bool bwd_res1 = !(getenv("TTSC_LSTM_BWD_RESIDENT") && atoi(getenv("TTSC_LSTM_BWD_RESIDENT")) == 0);
-    if (bwd_res1 && (H == 64 || H == 128)) {   // the slice's column of W_hh^T in registers, four k-slices per unit
+    if (path.id == TTSC_LSTM_PATH_RESIDENT) {   // the slice's column of W_hh^T in registers, four k-slices per unit
         if (H == 64)
             hipLaunchKernelGGL(lstm_bwd_resident_kernel<64>, dim3((unsigned)B, (unsigned)ndir), dim3(256), 0, (hipStream_t)stream, a);
         else
@@ -1258,12 +1327,8 @@ static int lstm_forward_impl(const float* xg_dev, const float* whh_packed_dev, f
     TTSC_REQUIRE(B > 0 && T > 0 && ndir >= 1 && ndir <= 2 && H >= 4 && H <= 512 && H % 4 == 0, "ttsc_lstm_seq_forward: bad shape B=%d T=%d H=%d ndir=%d", B, T, H, ndir);
     TTSC_REQUIRE(ldy >= (int64_t)yoff + (int64_t)ndir * H, "ttsc_lstm_seq_forward: ldy too small");
     LstmArgs a{xg_dev, whh_packed_dev, y_dev, lengths_dev, hn_dev, cn_dev, h0_dev, c0_dev, B, T, H, ndir, (int)ldy, yoff, gates_dev, c_dev};
-    // The split changes the summation order with G, so a result is bit-reproducible only among launches that pick the same
-    // G: always the case up to 64 (utterance, direction) pairs per launch (G = 4), e.g. a padded batch of <= 32 sentences
-    // against the same sentences run alone (tests/test_lstm_gpu.py, tests/test_api_gpu.py); larger batches (G = 2 / 1)
-    // agree to ~1e-6 relative.  TTSC_LSTM_SPLIT_INFER=0 keeps inference on the single-workgroup kernel.
-    static const bool split_infer = !(getenv("TTSC_LSTM_SPLIT_INFER") && atoi(getenv("TTSC_LSTM_SPLIT_INFER")) == 0);
-    if (H == 64 || H == 128) {   // W_hh resident in registers, one thread per gate row (same kernel for every batch size)
+    const LstmPath path = lstm_fwd_path(B, ndir, H, gates_dev != nullptr);
+    if (path.id == TTSC_LSTM_PATH_RESIDENT) {   // W_hh resident in registers, one thread per gate row (same kernel for every batch size)
         dim3 grid((unsigned)B, (unsigned)ndir);
         if (H == 64)
             hipLaunchKernelGGL(lstm_seq_resident_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -1276,70 +1341,46 @@ static int lstm_forward_impl(const float* xg_dev, const float* whh_packed_dev, f
         }
         return TTSC_OK;
     }
-    static const bool resident = !(getenv("TTSC_LSTM_RESIDENT") && atoi(getenv("TTSC_LSTM_RESIDENT")) == 0);
-    if ((gates_dev || split_infer) && resident && (H == 256 || H == 512)) {
-        // H = 256 / 512: G = 4 / 16 members per (utterance, direction), each thread holding 128 weights of W_hh in registers
-        // (lstm_seq_split_res_kernel: 512 threads = HU units x KS k-slices of 32).  All members of a launch must be resident, so a
-        // launch takes cus / G pairs; up to three consecutive launches still beat the streaming kernels (H = 256: 3 us per step
-        // and layer per launch against 9.8), and every batch size up to 3 * cus / (2 G) sentences then sums in the same order as
-        // a sentence run alone.
-        const int cus = device_cus();
-        if (cus >= 4) {
-            const int Gm = H == 256 ? 4 : 16;
-            const int pairs = B * ndir, cap = cus / Gm;
-            // utterances per member group (lstm_seq_split_res_nb_kernel: per utterance the same arithmetic as NB = 1).  Default: the smallest of
-            // 1 / 2 / 4 that fits the batch into ONE launch (shortest step), else 4 and up to three launches.  ttsc_lstm_set_group_size(n) asks
-            // for n per group whenever the batch has that many: fewer CUs held for a somewhat longer step — what a caller wants who runs the
-            // recurrence beside a kernel that fills the chip (Cubegan.inference_pipelined).
-            const int pref = g_lstm_group_size.load(std::memory_order_relaxed);
-            int NB = 1;
-            if (pref > 0) {
-                while (NB * 2 <= pref && NB * 2 <= B) NB *= 2;
-                while (NB < 8 && ((B + NB - 1) / NB) * ndir > 3 * cap) NB *= 2;
-            } else {
-                while (NB < 4 && ((B + NB - 1) / NB) * ndir > cap) NB *= 2;
-            }
-            const int groups = ((B + NB - 1) / NB) * ndir;
-            if (cap >= 1 && groups <= 3 * cap && pairs <= 16384) {
-                // granule ring [pairs][2 slots][H]: sized for this launch, grown on demand, one per (device, stream)
-                HandoffArea* ar = lstm_area((hipStream_t)stream, (size_t)pairs * 2 * H * sizeof(lstm_u64), true);
-                if (!ar) {
-                    set_error("ttsc_lstm_seq_forward: cannot allocate the hand-off counters / ring");
-                    return TTSC_ENOMEM;
-                }
-                lstm_u64* ring = reinterpret_cast<lstm_u64*>(ar->buf);
-                LstmSplitArgs sa{};
-                sa.f = a;
-                sa.cnt = ar->words;
-                sa.abort_word = ar->abort_word();
-                sa.G = Gm;
-                sa.HU = H / Gm;
-                sa.KS = 512 / sa.HU;
-                const size_t lds = ((size_t)NB * ((size_t)H + (size_t)sa.KS * 4 * sa.HU) + (size_t)NB * 4 * sa.HU) * sizeof(float);
-                for (int p0 = 0; p0 < groups; p0 += cap) {
-                    sa.p0 = p0;
-                    const int n = groups - p0 < cap ? groups - p0 : cap;
-                    const dim3 grid((unsigned)Gm, (unsigned)n, 1u);
-                    if (NB == 1)
-                        hipLaunchKernelGGL(lstm_seq_split_res_kernel<32>, grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
-                    else if (NB == 2)
-                        hipLaunchKernelGGL((lstm_seq_split_res_nb_kernel<32, 2>), grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
-                    else if (NB == 4)
-                        hipLaunchKernelGGL((lstm_seq_split_res_nb_kernel<32, 4>), grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
-                    else
-                        hipLaunchKernelGGL((lstm_seq_split_res_nb_kernel<32, 8>), grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
-                }
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) {
-                    set_error("lstm_seq_split_res_kernel launch failed: %s", hipGetErrorString(e));
-                    return TTSC_EHIP;
-                }
-                return TTSC_OK;
-            }
+    if (path.id == TTSC_LSTM_PATH_SPLIT_RES || path.id == TTSC_LSTM_PATH_SPLIT_RES_NB) {
+        const int Gm = path.G, NB = path.NB, cap = path.cap;
+        const int pairs = B * ndir, groups = ((B + NB - 1) / NB) * ndir;
+        // granule ring [pairs][2 slots][H]: sized for this launch, grown on demand, one per (device, stream)
+        HandoffArea* ar = lstm_area((hipStream_t)stream, (size_t)pairs * 2 * H * sizeof(lstm_u64), true);
+        if (!ar) {
+            set_error("ttsc_lstm_seq_forward: cannot allocate the hand-off counters / ring");
+            return TTSC_ENOMEM;
         }
+        lstm_u64* ring = reinterpret_cast<lstm_u64*>(ar->buf);
+        LstmSplitArgs sa{};
+        sa.f = a;
+        sa.cnt = ar->words;
+        sa.abort_word = ar->abort_word();
+        sa.G = Gm;
+        sa.HU = H / Gm;
+        sa.KS = 512 / sa.HU;
+        const size_t lds = ((size_t)NB * ((size_t)H + (size_t)sa.KS * 4 * sa.HU) + (size_t)NB * 4 * sa.HU) * sizeof(float);
+        for (int p0 = 0; p0 < groups; p0 += cap) {
+            sa.p0 = p0;
+            const int n = groups - p0 < cap ? groups - p0 : cap;
+            const dim3 grid((unsigned)Gm, (unsigned)n, 1u);
+            if (NB == 1)
+                hipLaunchKernelGGL(lstm_seq_split_res_kernel<32>, grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
+            else if (NB == 2)
+                hipLaunchKernelGGL((lstm_seq_split_res_nb_kernel<32, 2>), grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
+            else if (NB == 4)
+                hipLaunchKernelGGL((lstm_seq_split_res_nb_kernel<32, 4>), grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
+            else
+                hipLaunchKernelGGL((lstm_seq_split_res_nb_kernel<32, 8>), grid, dim3(512), lds, (hipStream_t)stream, sa, ring);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            set_error("lstm_seq_split_res_kernel launch failed: %s", hipGetErrorString(e));
+            return TTSC_EHIP;
+        }
+        return TTSC_OK;
     }
-    const int G = (gates_dev || split_infer) ? lstm_split_members(B, ndir, H) : 1;
-    if (G > 1) {
+    if (path.id == TTSC_LSTM_PATH_SPLIT) {
+        const int G = path.G;
         TTSC_REQUIRE(B * ndir <= 8192, "ttsc_lstm_seq_forward: too many sequences for the split kernel");
         HandoffArea* ar = lstm_area((hipStream_t)stream, 0);
         TTSC_REQUIRE(ar, "ttsc_lstm_seq_forward: cannot allocate the hand-off counters");
@@ -1360,7 +1401,7 @@ static int lstm_forward_impl(const float* xg_dev, const float* whh_packed_dev, f
         return TTSC_OK;
     }
     const int threads = (int)round_up(H, 64);
-    const int bt = B * ndir > 512 ? 2 : 1;
+    const int bt = path.NB;
     dim3 grid((unsigned)ceil_div(B, bt), (unsigned)ndir);
     const size_t lds = (size_t)2 * bt * H * sizeof(float);
     if (bt == 1)

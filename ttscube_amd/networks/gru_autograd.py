@@ -57,8 +57,12 @@ class HipGRUFn(torch.autograd.Function):
         gi2, gh2 = dgi.reshape(B * T, 3 * H), dgh.reshape(B * T, 3 * H)
         dx = gemm_hip(gi2, wih).reshape(x.shape) if ctx.needs_input_grad[0] else None       # dGi . W_ih                       (NN)
         dwih = gemm_hip(gi2, x.reshape(B * T, -1), trans_a=True)                             # dGi^T . x, split over the B*T rows (TN)
-        # dGh^T . h_prev with h_prev[b, t] = y[b, t-1] (0 at t = 0): the GEMM reads y one row up inside every sequence
-        dwhh = gemm_hip(gh2, y.reshape(B * T, H), trans_a=True, b_row_shift=-1, b_period=T)
+        # dGh^T . h_prev with h_prev[b, t] = y[b, t-1] (0 at t = 0): the GEMM reads y one row up inside every sequence.  A one-step
+        # sequence only sees the zero initial state (and the GEMM's row shift needs a period above 1): dW_hh = 0
+        if T > 1:
+            dwhh = gemm_hip(gh2, y.reshape(B * T, H), trans_a=True, b_row_shift=-1, b_period=T)
+        else:
+            dwhh = torch.zeros_like(whh)
         return dx, dwih, dwhh, colsum_hip(gi2), colsum_hip(gh2)
 
 

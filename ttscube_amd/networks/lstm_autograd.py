@@ -71,8 +71,12 @@ class HipLSTMLayerFn(torch.autograd.Function):
         for d in range(nd):
             sl = slice(d * 4 * H, (d + 1) * 4 * H)
             # dG_d^T . h_prev: the forward direction's previous step is t - 1, the reverse direction's t + 1 — a row shift of the
-            # direction's column slice of y inside every sequence (zero at the sequence's first step), nothing is materialised
-            dwhh = gemm_hip(dG2[:, sl], y2[:, d * H:(d + 1) * H], trans_a=True, b_row_shift=-1 if d == 0 else 1, b_period=T)
+            # direction's column slice of y inside every sequence (zero at the sequence's first step), nothing is materialised.  A one-step
+            # sequence only sees the zero initial state (and the GEMM's row shift needs a period above 1): dW_hh = 0
+            if T > 1:
+                dwhh = gemm_hip(dG2[:, sl], y2[:, d * H:(d + 1) * H], trans_a=True, b_row_shift=-1 if d == 0 else 1, b_period=T)
+            else:
+                dwhh = torch.zeros_like(whh[d])
             grads += [dwih[sl], dwhh, db[sl], db[sl]]
         return (dx, None) + tuple(grads)
 
