@@ -636,13 +636,14 @@ int ttsc_cond_input(const float* g_dev, const int32_t* f2p_dev, const int32_t* f
  *   ttsc_stft_mag            reim [M, 2*NB] (re | im) -> mag [M, ldm] = sqrt(re^2 + im^2 + eps)  (columns >= NB zeroed)
  *   ttsc_stft_mag_backward   d(re|im) = dmag * (re|im) / mag
  *   ttsc_log_clamp           y = scale * ln(max(x, minv))  (scale 1: natural log; 1/ln 10: log10);  _backward: dx = dy*scale/x above minv
- *   ttsc_overlap_add         backward of the framing: y [B, Lp] += frames [B, F, n_fft] at hop (fixed summation order) */
+ *   ttsc_overlap_add         backward of the framing: y [B, Lp] = sum of frames [B, F, n_fft] at hop (fixed summation order) over the first
+ *                            F_used rows of each utterance (the rest are rows of a batched DFT that straddle into the next utterance) */
 int ttsc_stft_mag(const float* reim_dev, int64_t M, int32_t NB, int32_t ldm, float eps, float* mag_dev, void* stream);
 int ttsc_stft_mag_backward(const float* dmag_dev, const float* reim_dev, const float* mag_dev, int64_t M, int32_t NB, int32_t ldm,
                            float* dreim_dev, void* stream);
 int ttsc_log_clamp(const float* x_dev, int64_t n, float minv, float scale, float* y_dev, void* stream);
 int ttsc_log_clamp_backward(const float* dy_dev, const float* x_dev, int64_t n, float minv, float scale, float* dx_dev, void* stream);
-int ttsc_overlap_add(const float* frames_dev, int32_t B, int32_t F, int32_t n_fft, int32_t hop, int64_t Lp, float* y_dev, void* stream);
+int ttsc_overlap_add(const float* frames_dev, int32_t B, int32_t F, int32_t F_used, int32_t n_fft, int32_t hop, int64_t Lp, float* y_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -49,14 +49,16 @@ __global__ __launch_bounds__(256) void log_clamp_bwd_kernel(const float* __restr
         dx[i] = x[i] > minv ? dy[i] * scale / x[i] : 0.f;
 }
 
-// backward of the framing: y[b, t] = sum over frames f with f*hop <= t < f*hop + n_fft of frames[b, f, t - f*hop]   (gather
-// form: one thread per output sample, at most ceil(n_fft / hop) terms, fixed summation order -> deterministic)
-__global__ __launch_bounds__(256) void overlap_add_kernel(const float* __restrict__ frames, int F, int n_fft, int hop, long Lp,
+// backward of the framing: y[b, t] = sum over frames f < Fu with f*hop <= t < f*hop + n_fft of frames[b, f, t - f*hop]   (gather
+// form: one thread per output sample, at most ceil(n_fft / hop) terms, fixed summation order -> deterministic).  Utterance b's frames sit
+// F rows apart; rows Fu .. F - 1 (the batched DFT's rows that straddle into the next utterance) are never read, so nothing of the next
+// utterance's samples — a NaN or Inf included — reaches this one's gradient
+__global__ __launch_bounds__(256) void overlap_add_kernel(const float* __restrict__ frames, int F, int Fu, int n_fft, int hop, long Lp,
                                                           float* __restrict__ y) {
     const int b = blockIdx.y;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < Lp; t += (long)gridDim.x * blockDim.x) {
         long f_hi = t / hop;
-        if (f_hi > F - 1) f_hi = F - 1;
+        if (f_hi > Fu - 1) f_hi = Fu - 1;
         const long f_lo = t < n_fft ? 0 : (t - n_fft) / hop + 1;   // smallest f with f*hop + n_fft > t
         float s = 0.f;
         for (long f = f_lo; f <= f_hi; ++f) s += frames[((size_t)b * F + f) * n_fft + (t - f * hop)];
@@ -112,9 +114,11 @@ extern "C" int ttsc_log_clamp_backward(const float* dy_dev, const float* x_dev, 
     return TTSC_OK;
 }
 
-extern "C" int ttsc_overlap_add(const float* frames_dev, int32_t B, int32_t F, int32_t n_fft, int32_t hop, int64_t Lp, float* y_dev, void* stream) {
-    TTSC_REQUIRE(frames_dev && y_dev && B > 0 && F > 0 && n_fft > 0 && hop > 0 && Lp >= (int64_t)(F - 1) * hop + n_fft, "ttsc_overlap_add: bad argument");
-    hipLaunchKernelGGL(overlap_add_kernel, dim3(grid_for(Lp), (unsigned)B), dim3(256), 0, (hipStream_t)stream, frames_dev, F, n_fft, hop, (long)Lp,
+extern "C" int ttsc_overlap_add(const float* frames_dev, int32_t B, int32_t F, int32_t F_used, int32_t n_fft, int32_t hop, int64_t Lp, float* y_dev,
+                                void* stream) {
+    TTSC_REQUIRE(frames_dev && y_dev && B > 0 && F > 0 && F_used > 0 && F_used <= F && n_fft > 0 && hop > 0 && Lp >= (int64_t)(F - 1) * hop + n_fft,
+                 "ttsc_overlap_add: bad argument");
+    hipLaunchKernelGGL(overlap_add_kernel, dim3(grid_for(Lp), (unsigned)B), dim3(256), 0, (hipStream_t)stream, frames_dev, F, F_used, n_fft, hop, (long)Lp,
                        y_dev);
     TTSC_LAUNCH_CHECK("overlap_add_kernel");
     return TTSC_OK;

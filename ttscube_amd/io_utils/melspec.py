@@ -73,6 +73,17 @@ def _gemm(x_ptr, w, y, M, N, K, ldx, stream):
                'ttsc_linear_forward')
 
 
+def gemm_plan(B, Lp, n_fft, hop):
+    """how _MelFn runs the DFT of B padded signals of Lp samples: F frames per utterance at Fp rows apart, `batched` = one GEMM launch over all
+    B * Fp rows (else one launch per utterance), `vector` = float4 loads of the frame rows (ttsc_linear_forward takes them when K and ldx are
+    multiples of 4 and the row base is 16-byte aligned; the per-utterance launches start Lp floats apart)"""
+    F_ = (Lp - n_fft) // hop + 1
+    Fp = F_ if B == 1 else -(-Lp // hop)
+    batched = Fp != F_
+    vector = n_fft % 4 == 0 and hop % 4 == 0 and (batched or B == 1 or Lp % 4 == 0)
+    return dict(F=F_, Fp=Fp, batched=batched, vector=vector)
+
+
 class _MelFn(torch.autograd.Function):
     """y_pad [B, Lp] (already padded) -> scale * log(max(mel_basis . |STFT|, minv)) as [B, n_mels, F]"""
 
@@ -81,15 +92,16 @@ class _MelFn(torch.autograd.Function):
         L = _lib.lib()
         yp = yp.float().contiguous()
         B, Lp = yp.shape
-        F_ = (Lp - n_fft) // hop + 1
+        plan = gemm_plan(B, Lp, n_fft, hop)
+        F_, Fp = plan['F'], plan['Fp']
         dft, dft_t, mel, mel_t, nb, ldm = _bases(n_fft, win, sr, n_mels, fmin, fmax, yp.device)
         # Frames of one utterance sit at a constant stride `hop` inside its padded signal: the DFT reads them in place (no gather).  A BATCH is laid
         # out so that this holds across utterances too — every signal padded with zeros to a whole number Fp of hops, one zeroed n_fft tail behind the
         # last — and all B * Fp row positions go through ONE GEMM launch (round 5 looped over the utterances: 16 launches of 50 rows each per
         # spectrogram at the training step's b = 16, ~85 us apiece on a dozen workgroups, 2.7 ms of the step's main stream).  Rows F_ .. Fp - 1 of an
-        # utterance straddle its end: they are computed, carried through the element-wise passes and cut off at the end; their gradient is zero.
-        Fp = F_ if B == 1 else -(-Lp // hop)
-        if Fp == F_:
+        # utterance straddle its end: they are computed, carried through the element-wise passes and cut off at the end; the overlap-add of the
+        # backward pass skips them (they carry no gradient, and the next utterance's samples must not reach this one's).
+        if not plan['batched']:
             sig = yp
         else:
             sig = torch.zeros(B * Fp * hop + n_fft, dtype=torch.float32, device=yp.device)
@@ -100,7 +112,7 @@ class _MelFn(torch.autograd.Function):
         out = torch.empty((B, Fp, n_mels), dtype=torch.float32, device=yp.device)
         with _lib.on_device(yp.device):
             s = _lib.current_stream()
-            if Fp == F_:
+            if not plan['batched']:
                 for b in range(B):
                     _gemm(C.c_void_p(sig[b].data_ptr()), dft, reim[b], F_, 2 * nb, n_fft, hop, s)
             else:
@@ -136,7 +148,7 @@ class _MelFn(torch.autograd.Function):
             _lib.check(L.ttsc_stft_mag_backward(_lib.dev_ptr(dmag), _lib.dev_ptr(reim), _lib.dev_ptr(mag), B * Fp, nb, ldm, _lib.dev_ptr(dreim), s),
                        'mag_bwd')
             _gemm(_lib.dev_ptr(dreim), dft_t, dfr, B * Fp, n_fft, 2 * nb, 2 * nb, s)               # dframes = d(re|im) . basis
-            _lib.check(L.ttsc_overlap_add(_lib.dev_ptr(dfr), B, Fp, n_fft, hop, Lo, _lib.dev_ptr(dy), s), 'overlap_add')
+            _lib.check(L.ttsc_overlap_add(_lib.dev_ptr(dfr), B, Fp, F_, n_fft, hop, Lo, _lib.dev_ptr(dy), s), 'overlap_add')
         return (dy[:, :Lp],) + (None,) * 10
 
 
