@@ -4,9 +4,12 @@ HiFi-GAN inference, batch = 64 utterances x 8 s (800 mel frames, hop 240 @ 24 kH
 fp32, on N MI355X GPUs (one process per GPU; utterance shards, no data-path collective -> weak scaling).
 
 A "step" is one generator forward over one resident batch of synthetic mels (inputs already in HBM).
-Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with the headline figure and the `roofline` figures derived from the timed steps.  A plain run only sets up, warms
+up, times the steps (and dumps their outputs if asked); `--full` adds everything that takes runs of its own: the oracle check of the output, the
+sustained-MFMA probe, the secondary legs (`extra`), the exact-fp32 run, the live rocprofv3 counter passes and the CPU baseline.
 
-    python bench.py                       # N=1
+    python bench.py                       # N=1, headline only
+    python bench.py --full                # N=1, headline + every secondary measurement and check (a few minutes)
     python bench.py --dump-outputs bench_outputs   # also write the last timed step's outputs as bench_outputs/<name>.npy (compare two builds output for output)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -728,9 +731,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--batch', type=int, default=64, help='utterances per GPU')
     ap.add_argument('--frames', type=int, default=800, help='mel frames per utterance (800 = 8 s)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the secondary legs (fp32, B=1, WaveRNN)')
-    ap.add_argument('--no-live-traffic', action='store_true', help='keep roofline.traffic from the committed PMC summary instead of measuring it with two rocprofv3 --pmc child passes (N = 1, default run only)')
+    ap.add_argument('--full', action='store_true',
+                    help='--mode infer: after the timed steps also check the output against the oracle, measure the sustained MFMA rate, run the secondary '
+                         'legs (B=1, WaveRNN, training steps, e2e, exact fp32), measure roofline.traffic live and time the CPU baseline (N = 1 for the legs, '
+                         'the traffic and the baseline).  Without it the run stops after the timed steps')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the secondary legs (fp32, B=1, WaveRNN) and the live traffic passes')
+    ap.add_argument('--no-live-traffic', action='store_true', help='--full: keep roofline.traffic from the committed PMC summary instead of measuring it with rocprofv3 --pmc child passes (N = 1)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy: the waveforms (infer: [batch, 1, samples]; '
                          'e2e: the shard\'s sentences concatenated in sentence order, with their lengths) or the step\'s losses (train); at most 64 MB in all, '
@@ -809,7 +816,7 @@ def main():
     dev_ms = ev0.elapsed_time(ev1)  # HIP events on the stream the kernels run on (torch current stream)
     dumped = dump_outputs(args.dump_outputs, {'waveform': out}) if args.dump_outputs and rank == 0 else None
     assert bool(torch.isfinite(out).all())
-    check_rms = self_check(g, mel, out, h, sd) if rank == 0 else None   # never report a time for wrong results
+    check_rms = self_check(g, mel, out, h, sd) if rank == 0 and args.full else None   # --full: never report a time for wrong results
 
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -865,7 +872,7 @@ def main():
         res['self_check_rms_vs_oracle'] = check_rms
         if dumped is not None:
             res['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
-        if precision == 'f16x3':
+        if precision == 'f16x3' and args.full:
             # What the matrix pipe of THIS device sustains, measured now (csrc/probe.hip: register-only v_mfma_f32_32x32x16_f16 loop on every CU):
             # MI355X clocks to its power budget, so operands with real bit patterns run well below the nominal peak that `peak` must quote.
             # `frac` stays achieved / nominal; `frac_of_sustained` prices the same number against the split-mix loop measured in this run.
@@ -884,7 +891,7 @@ def main():
                                                      'split-precision kernel has on this chip at its power budget')
             except Exception as e:
                 res['roofline']['sustained_f16_mfma_tflops'] = {'error': str(e)[:200]}
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             res['extra'] = extra_legs(g, h, sd, dev, R)
             if precision == 'f16x3':   # the same workload on the exact fp32 MFMA (k-ordered fmaf chain), for the record
                 try:
@@ -897,7 +904,7 @@ def main():
                     g.set_precision('f16x3')
                 except Exception as e:
                     res['extra']['exact_fp32_same_workload'] = {'error': str(e)[:200]}
-        if world == 1 and not args.no_extra and not args.no_live_traffic and precision == 'f16x3':
+        if world == 1 and args.full and not args.no_extra and not args.no_live_traffic and precision == 'f16x3':
             # roofline.traffic measured NOW (after every timed region of this process): two rocprofv3 --pmc child passes of this workload
             lt, detail = live_traffic(precision, B, T)
             if lt is not None:
@@ -912,7 +919,7 @@ def main():
                 res['roofline']['mfma_insts_per_forward']['source'] = 'SQ_INSTS_MFMA, rocprofv3 --pmc child pass of this run (bench.py::live_traffic)'
             else:
                 res['roofline']['traffic_live_error'] = detail
-        if world == 1 and not args.no_cpu_baseline:   # reported baseline: rank 0 at N=1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:   # reported baseline: rank 0 at N=1 only
             res['cpu_baseline'] = cpu_baseline(h, sd, mel)
         else:
             res['cpu_baseline'] = None

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 profile passes on the GPU box (run through gpurun): the headline bench under rocprofv3 (kernel trace + PMC passes: the generator's kernels are
 # round 5's, the records are re-taken on the final tree), the training step (kernel stats of the last steps, timeline), WaveRNN, the e2e path, and the
-# default / train / e2e bench lines.  A trimmed tools/profile_round.sh.      usage: bash tools/profile_r06.sh [r06]
+# `--full` / train / e2e bench lines.  A trimmed tools/profile_round.sh.      usage: bash tools/profile_r06.sh [r06]
 R=${1:-r06}
 O=gpurun_out/$R
 mkdir -p $O; cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
@@ -41,5 +41,5 @@ timeout 300 python bench.py --mode e2e --steps 5 --warmup 2 2>/dev/null | grep '
 timeout 300 python bench.py --mode train --steps 6 --warmup 2 2>/dev/null | grep '^{' > $O/bench_train_b16.json
 timeout 400 python bench.py --mode train --train-batch 128 --steps 3 --warmup 1 2>/dev/null | grep '^{' > $O/bench_train_b128.json
 timeout 200 python tools/bench_vocoder_step.py --iters 3 2>/dev/null < /dev/null | tail -1 > $O/vocoder_step.log
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err < /dev/null
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err < /dev/null
 du -sh $O; ls $O; tail -c 300 $O/bench_final.json

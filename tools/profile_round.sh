@@ -26,7 +26,7 @@ timeout 300 rocprofv3 --kernel-trace --stats -d $O/wr -o v -- python tools/bench
 python tools/rocpd_stats.py $O/wr/v_results.db $O/wavernn_kernel_stats.csv >> $O/wavernn.log 2>&1
 rm -rf $O/trace $O/fetch $O/write $O/sq $O/grbm $O/e2e $O/train $O/wr
 # the same workload on round 1's kernels only (no wide tiles, no fused chain), for the record
-(TTSC_CONV_WIDE=0 TTSC_HIFIGAN_CHAIN=0 timeout 200 $B --steps 5 --warmup 2) > $O/bench_r1_kernels.log 2>&1
+(TTSC_CONV_WIDE=0 TTSC_HIFIGAN_CHAIN=0 timeout -k 10 200 $B --full --steps 5 --warmup 2) > $O/bench_r1_kernels.log 2>&1
 timeout 300 python bench.py --mode train --steps 6 --warmup 2 2>/dev/null | grep '^{' > $O/bench_train_b16.json
 if [ -n "$FULL" ]; then
 timeout 400 python bench.py --mode train --train-batch 128 --steps 3 --warmup 1 2>/dev/null | grep '^{' > $O/bench_train_b128.json
@@ -50,11 +50,11 @@ rm -rf $O/voc
 (TTSC_CHAIN_IL=0 timeout 300 python tools/bench_stage.py --iters 5 --shapes 0,1,2,10,11,12 2>&1 | grep -v amdgpu.ids) > $O/bench_stage_random.log
 (TTSC_CHAIN_IL=0 timeout 300 python tools/bench_stage.py --iters 5 --shapes 0,1,10,12 --data zeros 2>&1 | grep -v amdgpu.ids) > $O/bench_stage_zeros.log
 (BENCH_CHAIN_SHAPES=10,11 timeout 300 python tools/bench_layers.py --stages 1,2,3 2>&1 | grep -v amdgpu.ids) > $O/layer_bench.log
-(TTSC_CHAIN_IL=0 timeout 200 $B --steps 5 --warmup 2) > $O/bench_plain_columns.log 2>&1
+(TTSC_CHAIN_IL=0 timeout -k 10 200 $B --full --steps 5 --warmup 2) > $O/bench_plain_columns.log 2>&1
 timeout 200 python tools/probes/textcoder_time.py > $O/textcoder_time.log 2>&1
 # the Cubegan step: host enqueue time vs GPU drain, with and without the text side on its own stream; the LSTM recurrence by utterances per member group
 (for t in 1 0; do echo "TTSC_TEXT_STREAM=$t"; TTSC_TEXT_STREAM=$t timeout 200 python tools/probes/train_host_bound.py 2>&1 | tail -1; done) > $O/train_host_bound.log
 (timeout 200 python tools/probes/lstm_group_probe.py 2>&1 | grep -v amdgpu.ids) > $O/lstm_group_probe.log
 (TTSC_GEMM_SPLIT=0 TTSC_LSTM_NB=1 timeout 300 python bench.py --mode e2e --steps 5 --warmup 2 --no-pipeline 2>/dev/null | grep '^{') > $O/bench_e2e_round3_text_side.json
-timeout 600 python bench.py > $O/bench_final.json 2> $O/bench_final.err < /dev/null
+timeout 600 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err < /dev/null
 du -sh $O; ls $O; tail -c 300 $O/bench_final.json
