@@ -645,6 +645,30 @@ int ttsc_log_clamp(const float* x_dev, int64_t n, float minv, float scale, float
 int ttsc_log_clamp_backward(const float* dy_dev, const float* x_dev, int64_t n, float minv, float scale, float* dx_dev, void* stream);
 int ttsc_overlap_add(const float* frames_dev, int32_t B, int32_t F, int32_t F_used, int32_t n_fft, int32_t hop, int64_t Lp, float* y_dev, void* stream);
 
+/* CubenetTextcoder training (cube/networks/textcoder.py:191-226; csrc/textcoder_train.hip).
+ *   ttsc_bn_tanh_dropout_train_forward   the PostNet block after a convolution in TRAINING mode, one launch: per-channel mean / biased
+ *                                        variance of x [B, C, F] over B x F (fixed order), y = keep * tanh(gamma x_hat + beta) / (1 - p),
+ *                                        running_mean / running_var updated with `momentum` (unbiased variance, as torch); mean / invstd saved.
+ *                                        mask_dev: {0,1} floats [B, C, F], or null = Philox-4x32-10 keyed by `seed`, counter word 2 = `layer`.
+ *                                        B * F must exceed 1 (torch's BatchNorm raises there too).
+ *   ttsc_bn_tanh_dropout_train_backward  dx, dgamma, dbeta from dy (the same mask / seed / layer as the forward call).
+ *   ttsc_textcoder_loss                  the step's four loss terms in one launch: out[0] CE(duration), out[1] CE(pitch) (mean over the rows whose
+ *                                        target is not ignore_index), out[2] mean|pre - t|, out[3] mean|post - t| (n values each, n % 4 == 0, 16-byte
+ *                                        aligned), and the gradients of all four operands.  A target outside [0, K) that is not ignore_index
+ *                                        contributes nothing and sets *status_dev |= 1 (duration) / 2 (pitch); no device assert.
+ *                                        Workspace: ttsc_textcoder_loss_workspace_bytes(Rd, Rp, n). */
+int ttsc_bn_tanh_dropout_train_forward(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* running_mean_dev, float* running_var_dev,
+                                       int32_t B, int32_t C, int32_t F, float momentum, float eps, float p, const float* mask_dev, uint64_t seed,
+                                       int32_t layer, float* y_dev, float* mean_dev, float* invstd_dev, void* stream);
+int ttsc_bn_tanh_dropout_train_backward(const float* dy_dev, const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev,
+                                        const float* invstd_dev, int32_t B, int32_t C, int32_t F, float p, const float* mask_dev, uint64_t seed,
+                                        int32_t layer, float* dx_dev, float* dgamma_dev, float* dbeta_dev, void* stream);
+size_t ttsc_textcoder_loss_workspace_bytes(int32_t Rd, int32_t Rp, int64_t n);
+int ttsc_textcoder_loss(const float* dur_logits_dev, const int64_t* dur_target_dev, int32_t Rd, int32_t Kd, const float* pitch_logits_dev,
+                        const int64_t* pitch_target_dev, int32_t Rp, int32_t Kp, const float* pre_dev, const float* post_dev, const float* mel_target_dev,
+                        int64_t n, int64_t ignore_index, float* out_dev, float* g_dur_dev, float* g_pitch_dev, float* g_pre_dev, float* g_post_dev,
+                        int32_t* status_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

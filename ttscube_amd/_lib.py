@@ -220,6 +220,13 @@ SIGNATURES = {
     'ttsc_melar_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     'ttsc_melar_destroy': (None, [C.c_void_p]),
+    'ttsc_bn_tanh_dropout_train_forward': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_void_p, C.c_uint64, C.c_int32]
+                                           + [C.c_void_p] * 4),
+    'ttsc_bn_tanh_dropout_train_backward': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_uint64, C.c_int32]
+                                            + [C.c_void_p] * 4),
+    'ttsc_textcoder_loss_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
+    'ttsc_textcoder_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 

@@ -36,6 +36,9 @@ class CubenetTextcoder(nn.Module):
         self._prenet = PreNet(80, 256, 2)
         self._postnet = PostNet(80)
         self._hip = {}
+        self._val_loss_durs = self._val_loss_pitch = self._val_loss_mel = 9999
+        self._val_loss_total = 999
+        self._loaded_optimizer_state = None
 
     def _lstm(self, name):
         if name not in self._hip:
@@ -146,8 +149,12 @@ class CubenetTextcoder(nn.Module):
         return torch.cat(outs, dim=1).reshape(1, -1, 80).contiguous()
 
     def forward(self, X, dropout_masks=None):
-        """Teacher-forced path (textcoder.py:100-138), inference numerics (no autograd): returns
-        (output_dur, output_pitch, output_mel, output_mel_post)."""
+        """Teacher-forced path (textcoder.py:100-138): returns (output_dur, output_pitch, output_mel, output_mel_post).  In training mode with
+        grad enabled: the differentiable path (networks/textcoder_train.py; dropout_masks: its {'prenet': ..., 'postnet': ...} dict); otherwise
+        inference numerics (no autograd)."""
+        if self.training and torch.is_grad_enabled():
+            from .textcoder_train import textcoder_forward_train
+            return textcoder_forward_train(self, X, dropout_masks)
         dev = self._get_device()
         x_char, x_speaker = X['x_char'].to(dev), X['x_speaker'].to(dev)
         B = x_char.shape[0]
@@ -167,6 +174,50 @@ class CubenetTextcoder(nn.Module):
             y = self._lstm('_mel_rnn')(torch.cat([h[:, :m], cond[:, :m]], dim=-1).contiguous())
             mel = linear_hip(y, self._mel_output.linear_layer.weight, self._mel_output.linear_layer.bias).reshape(B, -1, 80).contiguous()
             return out_dur, out_pitch, mel, self._postnet(mel, add_residual=True)
+
+    # ---- the LightningModule surface the reference's trainer drives (textcoder.py:191-270; scripts/train_textcoder.py) ----------------------
+    # The step logic lives in networks/textcoder_train.py (HIP kernels end to end).  `optimizers()` hands out what `configure_optimizers()` built;
+    # `log_dict` is a no-op unless a logger was attached with `set_logger`.
+    def configure_optimizers(self):
+        """textcoder.py:269-270: Adam(lr) as optim.FlatAdamW(weight_decay=0); restores a `.opt.last` state queued in `_loaded_optimizer_state`"""
+        from .textcoder_train import textcoder_configure_optimizers
+        self._optimizer = textcoder_configure_optimizers(self)
+        return self._optimizer
+
+    def optimizers(self):
+        if getattr(self, '_optimizer', None) is None:
+            self.configure_optimizers()
+        return self._optimizer
+
+    def set_logger(self, fn):
+        self._log_fn = fn
+
+    def log_dict(self, d, **kw):
+        fn = getattr(self, '_log_fn', None)
+        if fn is not None:
+            fn(d)
+
+    def training_step(self, batch, batch_ids=None, dropout_masks=None):
+        """textcoder.py:191-226 -> {'loss', 'l_mel', 'l_pitch', 'l_dur'} (read back when first looked at: training.StepLosses)"""
+        from .textcoder_train import textcoder_training_step
+        out = textcoder_training_step(self, batch, self.optimizers(), dropout_masks)
+        self.log_dict(out, prog_bar=True)
+        return out
+
+    def validation_step(self, batch, batch_ids=None):
+        """textcoder.py:228-251 (run it in eval mode, as Lightning does)"""
+        from .textcoder_train import textcoder_validation_step
+        out = textcoder_validation_step(self, batch)
+        self.log_dict(out, prog_bar=True)
+        return out
+
+    def validation_epoch_end(self, outputs) -> None:
+        """textcoder.py:253-261"""
+        n = len(outputs)
+        self._val_loss_total = sum(o['loss'] for o in outputs) / n
+        self._val_loss_mel = sum(o['l_mel'] for o in outputs) / n
+        self._val_loss_pitch = sum(o['l_pitch'] for o in outputs) / n
+        self._val_loss_durs = sum(o['l_dur'] for o in outputs) / n
 
     @torch.jit.ignore
     def save(self, path):
