@@ -310,6 +310,21 @@ def dev_ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+_SPLIT_FAMILIES = ((1, 'LSTM'), (2, 'GRU'), (4, 'mel-AR'), (8, 'other'))
+
+
+def _raise_split_status(where, m):
+    """Raise the TTSCError of status mask m: bits 1 | 2 | 4 | 8 = a hand-off of that family's split recurrence timed out, 16 = the split-precision
+    GEMM's range word is set; nothing for 0."""
+    if m & 15:
+        kinds = '/'.join(n for b, n in _SPLIT_FAMILIES if m & b)
+        raise TTSCError('%s: split %s recurrence aborted on a hand-off timeout (are other kernels occupying the CUs? '
+                        'TTSC_LSTM_SPLIT=1 / TTSC_GRU_SPLIT=1 select the single-workgroup kernels)' % (where, kinds))
+    if m & 16:
+        raise TTSCError('%s: an operand of a split-precision GEMM (ttsc_linear_forward_split) lay beyond the fp16 range (|v| > 65504) or was not '
+                        'finite — its results are invalid; TTSC_GEMM_SPLIT=0 keeps these projections on the exact fp32 kernel' % where)
+
+
 def check_split_status(where, stream=None):
     """Raise if a multi-workgroup recurrence (split LSTM / GRU kernels) gave up on an inter-workgroup hand-off since the last
     check — its outputs are then invalid.  Synchronises the device: call once per training step / synthesis, not per layer.
@@ -319,18 +334,11 @@ def check_split_status(where, stream=None):
         m = int(L.ttsc_split_status_stream(C.c_void_p(stream)))
         if m < 0:
             raise TTSCError('%s: ttsc_split_status_stream failed: %s' % (where, L.ttsc_last_error().decode()))
-        if m:
-            kinds = '/'.join(n for b, n in ((1, 'LSTM'), (2, 'GRU'), (4, 'mel-AR'), (8, 'other')) if m & b)
-            raise TTSCError('%s: split %s recurrence aborted on a hand-off timeout (are other kernels occupying the CUs? '
-                            'TTSC_LSTM_SPLIT=1 / TTSC_GRU_SPLIT=1 select the single-workgroup kernels)' % (where, kinds))
-        return
-    bad = [n for n, f in (('LSTM', L.ttsc_lstm_split_status), ('GRU', L.ttsc_gru_split_status), ('mel-AR', L.ttsc_melar_split_status)) if f() != 0]
-    if bad:
-        raise TTSCError('%s: split %s recurrence aborted on a hand-off timeout (are other kernels occupying the CUs? '
-                        'TTSC_LSTM_SPLIT=1 / TTSC_GRU_SPLIT=1 select the single-workgroup kernels)' % (where, '/'.join(bad)))
-    if L.ttsc_gemm_split_status() != 0:
-        raise TTSCError('%s: an operand of a split-precision GEMM (ttsc_linear_forward_split) lay beyond the fp16 range (|v| > 65504) or was not '
-                        'finite — its results are invalid; TTSC_GEMM_SPLIT=0 keeps these projections on the exact fp32 kernel' % where)
+        return _raise_split_status(where, m)
+    m = sum(b for b, f in ((1, L.ttsc_lstm_split_status), (2, L.ttsc_gru_split_status), (4, L.ttsc_melar_split_status)) if f() != 0)
+    if not m and L.ttsc_gemm_split_status() != 0:   # (read only when the recurrences are clean, as ever: reading clears it)
+        m = 16
+    _raise_split_status(where, m)
 
 
 class _StagingRing:
@@ -405,14 +413,7 @@ def check_split_status_once(where):
     host.copy_(word, non_blocking=True)
     word.zero_()
     torch.cuda.current_stream().synchronize()
-    m = int(host[0])
-    if m & 15:
-        kinds = '/'.join(k for b, k in ((1, 'LSTM'), (2, 'GRU'), (4, 'mel-AR'), (8, 'other')) if m & b)
-        raise TTSCError('%s: split %s recurrence aborted on a hand-off timeout (are other kernels occupying the CUs? '
-                        'TTSC_LSTM_SPLIT=1 / TTSC_GRU_SPLIT=1 select the single-workgroup kernels)' % (where, kinds))
-    if m & 16:
-        raise TTSCError('%s: an operand of a split-precision GEMM (ttsc_linear_forward_split) lay beyond the fp16 range (|v| > 65504) or was not '
-                        'finite — its results are invalid; TTSC_GEMM_SPLIT=0 keeps these projections on the exact fp32 kernel' % where)
+    _raise_split_status(where, int(host[0]))
 
 
 class lstm_group_size:

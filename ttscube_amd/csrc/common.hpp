@@ -55,6 +55,14 @@ int handoff_status(const char* tag);
 // the same for the areas of every tag that belong to `stream`, waiting for that stream only; bit mask lstm 1 | gru 2 | melar 4
 int handoff_status_stream(hipStream_t stream);
 
+// ---- weight upload of the handles that keep their parameters on the device (wavernn.hip, melar.hip) ----------------------------
+// (re)allocates *dst for n floats and copies them from the host
+int upload(float** dst, const float* host, size_t n);
+// host [rows, ld] (columns c0 .. c0+K, K % 4 == 0) -> device [K/4][rows][4]: thread `row` of the matvec chain (rnn_chain.hpp) reads four
+// consecutive k as one 16-byte load
+int upload_packed4(float** dst, const float* host, int64_t rows, int64_t ld, int64_t c0, int64_t K);
+inline int upload_packed4(float** dst, const float* host, int64_t rows, int64_t K) { return upload_packed4(dst, host, rows, K, 0, K); }
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 

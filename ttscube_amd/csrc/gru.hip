@@ -13,6 +13,7 @@
 
 #include "common.hpp"
 #include "../../include/ttscube_math.h"
+#include "handoff.hpp"
 #include "rnn_chain.hpp"
 
 namespace ttsc {
@@ -293,61 +294,12 @@ __global__ __launch_bounds__(512) void gru_bwd_split_kernel(GruSplitArgs s) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same split with the member's weights RESIDENT IN REGISTERS and the state handed over as 8-byte {value, step tag} granules that the
-// consumers poll directly (the scheme of lstm_seq_split_res_kernel / lstm_bwd_split_res_kernel): H = 512 over 16 members (all 256 CUs for 16
+// consumers poll directly (handoff.hpp; the scheme of lstm_seq_split_res_kernel / lstm_bwd_split_res_kernel): H = 512 over 16 members (all 256 CUs for 16
 // utterances) or H = 256 over 4 — 3 x 32 forward weights / 96 backward weights per thread.  The kernels above stream 768 KB (G = 4) of W_hh per
 // member and step from L2 and pay counter + data round trips: 8 + 12 us per time step at H = 512, i.e. 0.48 s for the vocoder's 24 000-step
 // training sequences.
-typedef unsigned long long gru_u64;
-typedef float gru_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool gru_poll(const gru_u64* src, unsigned tag, unsigned* abort_word, float* out) {
-    gru_u64 gq;
-    unsigned spins = 0;
-    for (;;) {
-        gq = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(gq >> 32) == tag) break;
-        if (++spins > GS_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(abort_word + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky copy
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    *out = __uint_as_float((unsigned)gq);
-    return true;
-}
-
-// Up to N granules per thread (src + i0 + r * stride for r < n) in ONE round trip: all loads are issued before the first tag is looked at, and only a pass in
-// which some granule is still missing is repeated.  gru_poll in a loop pays the L2 round trip once per granule even when every granule has arrived (the backward
-// recurrence hands over 3H values to 512 threads: three dependent round trips per step).
-template <int N>
-__device__ __forceinline__ bool gru_poll_n(const gru_u64* src, int i0, int stride, int n, unsigned tag, unsigned* abort_word, float* out) {
-    gru_u64 g[N];
-    unsigned spins = 0;
-    for (;;) {
-#pragma unroll
-        for (int r = 0; r < N; ++r)
-            if (r < n) g[r] = __hip_atomic_load(src + i0 + r * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool all = true;
-#pragma unroll
-        for (int r = 0; r < N; ++r)
-            if (r < n) all = all && ((unsigned)(g[r] >> 32) == tag);
-        if (all) break;
-        if (++spins > GS_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(abort_word + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky copy
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-#pragma unroll
-    for (int r = 0; r < N; ++r)
-        if (r < n) out[i0 + r * stride] = __uint_as_float((unsigned)g[r]);
-    return true;
-}
-
 template <int KL>   // inputs per k-slice = H / KS
-__global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, gru_u64* ring) {
+__global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, u64* ring) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // h[H] | part[KS][3][HU] | act[3][HU]
     const GruArgs& a = s.f;
     const int H = a.H, H3 = 3 * H, HU = s.HU, KS = s.KS;
@@ -357,10 +309,10 @@ __global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, 
     float* hs = sm;
     float* part = sm + H;
     float* act = part + KS * 3 * HU;   // [3][HU]: r, z, W_hn h + b_hn of this step
-    gru_u64* rg = ring + (size_t)b * 2 * H;
+    u64* rg = ring + (size_t)b * 2 * H;
     const bool owner = ks == 0;
     // gates r and z side by side: one v_pk_fma_f32 advances both k-ordered chains (per lane the fused multiply-add of the scalar form: same bits)
-    gru_f32x2 wrz[KL];
+    f32x2 wrz[KL];
     float wn[KL];
     {
         // packed [H/4][3H][4]: row g*H + j, k-block kb holds k = 4*kb .. 4*kb+3
@@ -370,10 +322,10 @@ __global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, 
             const float4 vr = w4[(size_t)(ks * (KL / 4) + kb) * H3];
             const float4 vz = w4[(size_t)(ks * (KL / 4) + kb) * H3 + H];
             const float4 vn = w4[(size_t)(ks * (KL / 4) + kb) * H3 + 2 * H];
-            wrz[4 * kb] = gru_f32x2{vr.x, vz.x};
-            wrz[4 * kb + 1] = gru_f32x2{vr.y, vz.y};
-            wrz[4 * kb + 2] = gru_f32x2{vr.z, vz.z};
-            wrz[4 * kb + 3] = gru_f32x2{vr.w, vz.w};
+            wrz[4 * kb] = f32x2{vr.x, vz.x};
+            wrz[4 * kb + 1] = f32x2{vr.y, vz.y};
+            wrz[4 * kb + 2] = f32x2{vr.z, vz.z};
+            wrz[4 * kb + 3] = f32x2{vr.w, vz.w};
             wn[4 * kb] = vn.x;
             wn[4 * kb + 1] = vn.y;
             wn[4 * kb + 2] = vn.z;
@@ -392,24 +344,28 @@ __global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, 
         if (owner) xg_n = xb[(size_t)t * H3 + 2 * H];
         bool fail = false;
         if (t > 0) {
-            const gru_u64* src = rg + (size_t)((t - 1) & 1) * H;
-            for (int i = tid; i < H; i += 512) fail = !gru_poll(src + i, (unsigned)t, s.abort_word, &hs[i]) || fail;
+            const u64* src = rg + (size_t)((t - 1) & 1) * H;
+            for (int i = tid; i < H; i += 512) {
+                float v[1];
+                fail = !poll_granules_strided<GS_SPIN_LIMIT, true>(src + i, 1, (unsigned)t, s.abort_word, v) || fail;
+                hs[i] = v[0];
+            }
         } else {
             for (int i = tid; i < H; i += 512) hs[i] = a.h_0 ? a.h_0[(size_t)b * H + i] : 0.f;
         }
         if (__syncthreads_or(fail)) return;
         const float hprev = owner ? hs[j] : 0.f;   // (hs is rewritten by the next step's poll while the owners are still combining)
-        gru_f32x2 arz = {0.f, 0.f};
+        f32x2 arz = {0.f, 0.f};
         float an = 0.f;
         {
             const float4* h4 = reinterpret_cast<const float4*>(hs + ks * KL);
 #pragma unroll
             for (int kb = 0; kb < KL / 4; ++kb) {
                 const float4 hv = h4[kb];
-                arz = __builtin_elementwise_fma(wrz[4 * kb], (gru_f32x2){hv.x, hv.x}, arz);
-                arz = __builtin_elementwise_fma(wrz[4 * kb + 1], (gru_f32x2){hv.y, hv.y}, arz);
-                arz = __builtin_elementwise_fma(wrz[4 * kb + 2], (gru_f32x2){hv.z, hv.z}, arz);
-                arz = __builtin_elementwise_fma(wrz[4 * kb + 3], (gru_f32x2){hv.w, hv.w}, arz);
+                arz = __builtin_elementwise_fma(wrz[4 * kb], (f32x2){hv.x, hv.x}, arz);
+                arz = __builtin_elementwise_fma(wrz[4 * kb + 1], (f32x2){hv.y, hv.y}, arz);
+                arz = __builtin_elementwise_fma(wrz[4 * kb + 2], (f32x2){hv.z, hv.z}, arz);
+                arz = __builtin_elementwise_fma(wrz[4 * kb + 3], (f32x2){hv.w, hv.w}, arz);
                 an = fmaf(wn[4 * kb], hv.x, an);
                 an = fmaf(wn[4 * kb + 1], hv.y, an);
                 an = fmaf(wn[4 * kb + 2], hv.z, an);
@@ -430,8 +386,7 @@ __global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, 
             const float r = act[u], z = act[HU + u], hl = act[2 * HU + u];
             const float n = ttsc_tanhf(fmaf(r, hl, xg_n));
             const float hv = fmaf(z, hprev - n, n);
-            __hip_atomic_store(rg + (size_t)(t & 1) * H + j, ((gru_u64)(unsigned)(t + 1) << 32) | (gru_u64)__float_as_uint(hv), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            st_granule(rg + (size_t)(t & 1) * H + j, hv, (unsigned)(t + 1));
             yb[(size_t)t * H + j] = hv;
             if (a.saved) {
                 float* sp = a.saved + ((size_t)b * a.T + t) * (4 * (size_t)H) + j;
@@ -445,7 +400,7 @@ __global__ __launch_bounds__(512) void gru_seq_split_res_kernel(GruSplitArgs s, 
 }
 
 template <int KL>   // gate rows per k-slice = 3H / KS
-__global__ __launch_bounds__(512) void gru_bwd_split_res_kernel(GruSplitArgs s, gru_u64* ring) {
+__global__ __launch_bounds__(512) void gru_bwd_split_res_kernel(GruSplitArgs s, u64* ring) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // dGh[3H] | part[KS][HU]
     const GruBwdArgs& a = s.bw;
     const int H = a.H, H3 = 3 * H, HU = s.HU, KS = s.KS;
@@ -454,7 +409,7 @@ __global__ __launch_bounds__(512) void gru_bwd_split_res_kernel(GruSplitArgs s, 
     const int j = m * HU + u;
     float* dg = sm;
     float* part = sm + H3;
-    gru_u64* rg = ring + (size_t)b * 2 * H3;
+    u64* rg = ring + (size_t)b * 2 * H3;
     const bool owner = ks == 0;
     float w[KL];
     {
@@ -489,7 +444,7 @@ __global__ __launch_bounds__(512) void gru_bwd_split_res_kernel(GruSplitArgs s, 
     if (owner) fetch(a.T - 1);
     for (int t = a.T - 1; t >= 0; --t) {
         const unsigned tag = (unsigned)(a.T - t);
-        gru_u64* slot = rg + (size_t)(t & 1) * H3;
+        u64* slot = rg + (size_t)(t & 1) * H3;
         float dh_direct = 0.f;
         if (owner) {
             const float r = pr, z = pz, n = pn, hl = phl, hp = php;
@@ -499,10 +454,10 @@ __global__ __launch_bounds__(512) void gru_bwd_split_res_kernel(GruSplitArgs s, 
             const float dr_pre = dn_pre * hl * r * (1.f - r);
             dh_direct = dh * z;
             if (t > 0) {   // hand-off first
-                const gru_u64 tg = (gru_u64)tag << 32;
-                __hip_atomic_store(slot + j, tg | (gru_u64)__float_as_uint(dr_pre), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(slot + H + j, tg | (gru_u64)__float_as_uint(dz_pre), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(slot + 2 * H + j, tg | (gru_u64)__float_as_uint(dn_pre * r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const u64 tg = granule_tag(tag);
+                st_granule_word(slot + j, dr_pre, tg);
+                st_granule_word(slot + H + j, dz_pre, tg);
+                st_granule_word(slot + 2 * H + j, dn_pre * r, tg);
             }
             float* gi = gib + (size_t)t * H3 + j;
             gi[0] = dr_pre;
@@ -517,8 +472,14 @@ __global__ __launch_bounds__(512) void gru_bwd_split_res_kernel(GruSplitArgs s, 
         if (owner) fetch(t - 1);   // in flight while the exchange completes
         bool fail = false;
         for (int i0 = tid; i0 < H3; i0 += 4 * 512) {   // (H = 512: all three granules of a thread in one round trip)
-            const int n = (H3 - i0 + 511) / 512;
-            fail = !gru_poll_n<4>(slot, i0, 512, n < 4 ? n : 4, tag, s.abort_word, dg) || fail;
+            int off[4];
+            unsigned mask = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                off[r] = i0 + r * 512;
+                mask |= off[r] < H3 ? 1u << r : 0u;
+            }
+            fail = !poll_granules_to<GS_SPIN_LIMIT, true>(slot, off, off, mask, tag, s.abort_word, dg) || fail;
         }
         if (__syncthreads_or(fail)) return;
         float x = 0.f;
@@ -658,9 +619,9 @@ extern "C" int ttsc_gru_seq_forward(const float* xg_dev, const float* whh_packed
     const int path = gru_train_path(B, H, &G);
     if (path == TTSC_GRU_PATH_SPLIT_RES) {
         const int Gr = G;
-        HandoffArea* ar = gru_ring_area((hipStream_t)stream, (size_t)B * 2 * H * sizeof(gru_u64));
+        HandoffArea* ar = gru_ring_area((hipStream_t)stream, (size_t)B * 2 * H * sizeof(u64));
         TTSC_REQUIRE(ar, "ttsc_gru_seq_forward: cannot allocate the hand-off ring");
-        TTSC_HIP_CHECK(hipMemsetAsync(ar->buf, 0, (size_t)B * 2 * H * sizeof(gru_u64), (hipStream_t)stream));
+        TTSC_HIP_CHECK(hipMemsetAsync(ar->buf, 0, (size_t)B * 2 * H * sizeof(u64), (hipStream_t)stream));
         GruSplitArgs sa{};
         sa.f = a;
         sa.cnt = ar->words;
@@ -669,7 +630,7 @@ extern "C" int ttsc_gru_seq_forward(const float* xg_dev, const float* whh_packed
         sa.HU = H / Gr;
         sa.KS = 512 / sa.HU;
         const size_t lds = ((size_t)H + (size_t)sa.KS * 3 * sa.HU + (size_t)3 * sa.HU) * sizeof(float);
-        hipLaunchKernelGGL(gru_seq_split_res_kernel<32>, dim3((unsigned)Gr, (unsigned)B), dim3(512), lds, (hipStream_t)stream, sa, reinterpret_cast<gru_u64*>(ar->buf));
+        hipLaunchKernelGGL(gru_seq_split_res_kernel<32>, dim3((unsigned)Gr, (unsigned)B), dim3(512), lds, (hipStream_t)stream, sa, reinterpret_cast<u64*>(ar->buf));
         return gru_check_launch("gru_seq_split_res_kernel");
     }
     if (path == TTSC_GRU_PATH_SPLIT) {
@@ -699,9 +660,9 @@ extern "C" int ttsc_gru_seq_backward(const float* dy_dev, const float* saved_dev
     const int path = gru_train_path(B, H, &G);
     if (path == TTSC_GRU_PATH_SPLIT_RES) {
         const int Gr = G;
-        HandoffArea* ar = gru_ring_area((hipStream_t)stream, (size_t)B * 2 * 3 * H * sizeof(gru_u64));
+        HandoffArea* ar = gru_ring_area((hipStream_t)stream, (size_t)B * 2 * 3 * H * sizeof(u64));
         TTSC_REQUIRE(ar, "ttsc_gru_seq_backward: cannot allocate the hand-off ring");
-        TTSC_HIP_CHECK(hipMemsetAsync(ar->buf, 0, (size_t)B * 2 * 3 * H * sizeof(gru_u64), (hipStream_t)stream));
+        TTSC_HIP_CHECK(hipMemsetAsync(ar->buf, 0, (size_t)B * 2 * 3 * H * sizeof(u64), (hipStream_t)stream));
         GruSplitArgs sa{};
         sa.bw = a;
         sa.cnt = ar->words;
@@ -710,7 +671,7 @@ extern "C" int ttsc_gru_seq_backward(const float* dy_dev, const float* saved_dev
         sa.HU = H / Gr;
         sa.KS = 512 / sa.HU;
         const size_t lds = ((size_t)3 * H + (size_t)sa.KS * sa.HU) * sizeof(float);
-        hipLaunchKernelGGL(gru_bwd_split_res_kernel<96>, dim3((unsigned)Gr, (unsigned)B), dim3(512), lds, (hipStream_t)stream, sa, reinterpret_cast<gru_u64*>(ar->buf));
+        hipLaunchKernelGGL(gru_bwd_split_res_kernel<96>, dim3((unsigned)Gr, (unsigned)B), dim3(512), lds, (hipStream_t)stream, sa, reinterpret_cast<u64*>(ar->buf));
         return gru_check_launch("gru_bwd_split_res_kernel");
     }
     if (path == TTSC_GRU_PATH_SPLIT) {

@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "../../include/ttscube_math.h"
+#include "handoff.hpp"
 #include "rnn_chain.hpp"
 
 namespace ttsc {
@@ -485,44 +486,11 @@ __global__ __launch_bounds__(512) void lstm_seq_split_kernel(LstmSplitArgs s) {
 }
 
 // The same split with the member's rows of W_hh RESIDENT IN REGISTERS (4 * KL <= 128 weights per thread: H = 256 over 4
-// members) and the state handed over as 8-byte {value, step tag} granules that the consumers poll directly (one agent-scope store
-// per value, no counter, no producer-side drain; ring of two slots per sequence, see wavernn_tile.hip for the argument why two
-// suffice).  Summation order = lstm_seq_split_kernel's (k-ordered chain per k-slice, slices added in order), so results are
+// members) and the state handed over as 8-byte {value, step tag} granules that the consumers poll directly (the granule protocol of
+// handoff.hpp; ring of two slots per sequence).  Summation order = lstm_seq_split_kernel's (k-ordered chain per k-slice, slices added in order), so results are
 // bit-identical to it; what changes is the step time: no 256 KB weight stream and one round trip instead of three per step.
-typedef unsigned long long lstm_u64;
-typedef float lstm_f32x2 __attribute__((ext_vector_type(2)));
-
-// Up to N granules per thread in ONE round trip: every load (src[off[r]] for the r set in `mask`) is issued before the first tag is looked at; a pass is repeated only while
-// some granule is missing.  Polling granule by granule pays the L2 round trip once per granule even when all of them have arrived (the backward recurrence
-// hands 4H values to 512 threads: two dependent round trips per step; the batched forward kernel NB * H).  Values land in out[dst[r]].
-template <int N>
-__device__ __forceinline__ bool lstm_poll_n(const lstm_u64* src, const int (&off)[N], const int (&dst)[N], unsigned mask, unsigned tag, unsigned* abort_word, float* out) {
-    lstm_u64 g[N];
-    unsigned spins = 0;
-    for (;;) {
-#pragma unroll
-        for (int r = 0; r < N; ++r)
-            if (mask >> r & 1u) g[r] = __hip_atomic_load(src + off[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool all = true;
-#pragma unroll
-        for (int r = 0; r < N; ++r)
-            if (mask >> r & 1u) all = all && ((unsigned)(g[r] >> 32) == tag);
-        if (all) break;
-        if (++spins > GS_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(abort_word + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky copy
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-#pragma unroll
-    for (int r = 0; r < N; ++r)
-        if (mask >> r & 1u) out[dst[r]] = __uint_as_float((unsigned)g[r]);
-    return true;
-}
-
 template <int KL>
-__global__ __launch_bounds__(512) void lstm_seq_split_res_kernel(LstmSplitArgs s, lstm_u64* ring) {
+__global__ __launch_bounds__(512) void lstm_seq_split_res_kernel(LstmSplitArgs s, u64* ring) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // h[H] | part[KS][4][HU] | act[4][HU]
     const LstmArgs& a = s.f;
     const int H = a.H, H4 = 4 * H, HU = s.HU, KS = s.KS;
@@ -532,13 +500,13 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_kernel(LstmSplitArgs s
     float* hs = sm;
     float* part = sm + H;
     float* act = part + KS * 4 * HU;   // [4][HU] activated gates of this step
-    lstm_u64* rg = ring + (size_t)pair * 2 * H;
+    u64* rg = ring + (size_t)pair * 2 * H;
     const bool owner = ks == 0;
     const int len = a.lengths ? a.lengths[b] : a.T;
     float* yb = a.y + (size_t)b * a.T * a.ldy + a.yoff + dir * H;
     // gate pairs (i, f) and (g, o) side by side: one v_pk_fma_f32 advances two of the four k-ordered chains of a thread (each lane of the packed
     // instruction is the fused multiply-add the scalar form issues: same bits, half the vector instructions of the step's 128)
-    lstm_f32x2 w[2][KL];
+    f32x2 w[2][KL];
     {
         // packed [H/4][4H][4]: row g*H + j, k-block kb holds k = 4*kb .. 4*kb+3
         const float4* w4 = reinterpret_cast<const float4*>(a.whh + (size_t)dir * H * H4) + j;
@@ -567,28 +535,17 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_kernel(LstmSplitArgs s
             xv = a.xg[((size_t)b * a.T + tpos) * ((size_t)a.ndir * H4) + (size_t)dir * H4 + (size_t)ks * H + j];
         bool fail = false;
         if (st > 0) {
-            const lstm_u64* src = rg + (size_t)((st - 1) & 1) * H;
+            const u64* src = rg + (size_t)((st - 1) & 1) * H;
             for (int i = tid; i < H; i += 512) {
-                lstm_u64 gq;
-                unsigned spins = 0;
-                for (;;) {
-                    gq = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((unsigned)(gq >> 32) == (unsigned)st) break;
-                    if (++spins > GS_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(s.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                        __hip_atomic_store(s.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(s.abort_word + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky copy
-                        fail = true;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                hs[i] = __uint_as_float((unsigned)gq);
+                float v[1];
+                fail = !poll_granules_strided<GS_SPIN_LIMIT, true>(src + i, 1, (unsigned)st, s.abort_word, v) || fail;
+                hs[i] = v[0];
             }
         } else {
             for (int i = tid; i < H; i += 512) hs[i] = a.h_0 ? a.h_0[((size_t)dir * a.B + b) * H + i] : 0.f;
         }
         if (__syncthreads_or(fail)) return;
-        lstm_f32x2 acc[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        f32x2 acc[2] = {{0.f, 0.f}, {0.f, 0.f}};
         {
             const float4* h4 = reinterpret_cast<const float4*>(hs + ks * KL);
 #pragma unroll
@@ -596,11 +553,11 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_kernel(LstmSplitArgs s
                 const float4 hv = h4[kb];
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
-                    lstm_f32x2 x = acc[gp];
-                    x = __builtin_elementwise_fma(w[gp][4 * kb], (lstm_f32x2){hv.x, hv.x}, x);
-                    x = __builtin_elementwise_fma(w[gp][4 * kb + 1], (lstm_f32x2){hv.y, hv.y}, x);
-                    x = __builtin_elementwise_fma(w[gp][4 * kb + 2], (lstm_f32x2){hv.z, hv.z}, x);
-                    x = __builtin_elementwise_fma(w[gp][4 * kb + 3], (lstm_f32x2){hv.w, hv.w}, x);
+                    f32x2 x = acc[gp];
+                    x = __builtin_elementwise_fma(w[gp][4 * kb], (f32x2){hv.x, hv.x}, x);
+                    x = __builtin_elementwise_fma(w[gp][4 * kb + 1], (f32x2){hv.y, hv.y}, x);
+                    x = __builtin_elementwise_fma(w[gp][4 * kb + 2], (f32x2){hv.z, hv.z}, x);
+                    x = __builtin_elementwise_fma(w[gp][4 * kb + 3], (f32x2){hv.w, hv.w}, x);
                     acc[gp] = x;
                 }
             }
@@ -618,8 +575,7 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_kernel(LstmSplitArgs s
             const float ig = act[u], fg = act[HU + u], gg = act[2 * HU + u], og = act[3 * HU + u];
             c = fmaf(fg, c, ig * gg);
             hlast = og * ttsc_tanhf(c);
-            __hip_atomic_store(rg + (size_t)(st & 1) * H + j, ((lstm_u64)(unsigned)(st + 1) << 32) | (lstm_u64)__float_as_uint(hlast), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            st_granule(rg + (size_t)(st & 1) * H + j, hlast, (unsigned)(st + 1));
             yb[(size_t)tpos * a.ldy + j] = hlast;
             if (a.gates_out) {
                 float* gp = a.gates_out + ((size_t)b * a.T + tpos) * ((size_t)a.ndir * H4) + (size_t)dir * H4 + j;
@@ -655,7 +611,7 @@ __device__ __forceinline__ void lstm_pkfma_hi(lstm_f2& acc, const lstm_f2& w, co
 }
 
 template <int KL, int NB>
-__global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArgs s, lstm_u64* ring) {
+__global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArgs s, u64* ring) {
     static_assert(NB == 2 || NB == 4 || NB == 8, "utterances per member group");
     extern __shared__ __attribute__((aligned(16))) float sm[];   // h[H][NB] (utterance-interleaved) | part[NB][KS][4][HU] | act[NB][4][HU]
     const LstmArgs& a = s.f;
@@ -684,7 +640,7 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArg
         olen = (q == ks) ? len[q] : olen;
         alen = (q == aq) ? len[q] : alen;
     }
-    lstm_u64* org = ring + (size_t)(ob * a.ndir + dir) * 2 * H;
+    u64* org = ring + (size_t)(ob * a.ndir + dir) * 2 * H;
     float* yb = a.y + (size_t)ob * a.T * a.ldy + a.yoff + dir * H;
     lstm_f2 w[4][KL / 2];
     {
@@ -743,21 +699,10 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArg
             // last value, which nothing reads) in one round trip; the first four are described by pb / pd / pl, set up before the loop
             if (NB * H <= 512) {   // one granule per thread (two utterances at H = 256, the padded batch's usual launch): the plain poll
                 if (tid < NB * H && st < pl[0]) {
-                    const lstm_u64* src = ring + pb[0] + ((st - 1) & 1) * H;
-                    lstm_u64 gq;
-                    unsigned spins = 0;
-                    for (;;) {
-                        gq = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if ((unsigned)(gq >> 32) == (unsigned)st) break;
-                        if (++spins > GS_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(s.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                            __hip_atomic_store(s.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(s.abort_word + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky copy
-                            fail = true;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    hs[pd[0]] = __uint_as_float((unsigned)gq);
+                    const u64* src = ring + pb[0] + ((st - 1) & 1) * H;
+                    float v[1];
+                    fail = !poll_granules_strided<GS_SPIN_LIMIT, true>(src, 1, (unsigned)st, s.abort_word, v);
+                    hs[pd[0]] = v[0];
                 }
             } else {
                 const int par = ((st - 1) & 1) * H;
@@ -768,7 +713,7 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArg
                     off[r] = pb[r] + par;
                     mask |= st < pl[r] ? 1u << r : 0u;
                 }
-                if (mask) fail = !lstm_poll_n<4>(ring, off, pd, mask, (unsigned)st, s.abort_word, hs) || fail;
+                if (mask) fail = !poll_granules_to<GS_SPIN_LIMIT, true>(ring, off, pd, mask, (unsigned)st, s.abort_word, hs) || fail;
             }
             for (int e0 = tid + 4 * 512; e0 < NB * H; e0 += 4 * 512) {   // (H = 512 with 8 utterances per group: a second round)
                 int off[4], dst[4];
@@ -789,7 +734,7 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArg
                         }
                     }
                 }
-                if (mask) fail = !lstm_poll_n<4>(ring, off, dst, mask, (unsigned)st, s.abort_word, hs) || fail;
+                if (mask) fail = !poll_granules_to<GS_SPIN_LIMIT, true>(ring, off, dst, mask, (unsigned)st, s.abort_word, hs) || fail;
             }
         }
         if (__syncthreads_or(fail)) return;
@@ -842,8 +787,7 @@ __global__ __launch_bounds__(512) void lstm_seq_split_res_nb_kernel(LstmSplitArg
             const float ig = aw[0], fg = aw[HU], gg = aw[2 * HU], og = aw[3 * HU];
             c = fmaf(fg, c, ig * gg);
             hlast = og * ttsc_tanhf(c);
-            __hip_atomic_store(org + (size_t)(st & 1) * H + j, ((lstm_u64)(unsigned)(st + 1) << 32) | (lstm_u64)__float_as_uint(hlast), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            st_granule(org + (size_t)(st & 1) * H + j, hlast, (unsigned)(st + 1));
             yb[(size_t)tpos * a.ldy + j] = hlast;
             if (a.gates_out) {
                 float* gp = a.gates_out + ((size_t)ob * a.T + tpos) * ((size_t)a.ndir * H4) + (size_t)dir * H4 + j;
@@ -939,7 +883,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_split_kernel(LstmSplitArgs s) {
 // two-slot ring that the consumers poll directly, and the owner threads fetch the saved gates / cell states / dy of step t-1 before they wait for
 // the exchange of step t.  Chain order = the streaming kernel's (k ascending per slice, slices added in order): results are bit-identical to it.
 template <int KL>
-__global__ __launch_bounds__(512) void lstm_bwd_split_res_kernel(LstmSplitArgs s, lstm_u64* ring) {
+__global__ __launch_bounds__(512) void lstm_bwd_split_res_kernel(LstmSplitArgs s, u64* ring) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // dg[4H] | part[KS][HU]
     const LstmBwdArgs& a = s.bw;
     const int H = a.H, H4 = 4 * H, HU = s.HU, KS = s.KS;
@@ -948,7 +892,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_split_res_kernel(LstmSplitArgs s
     const int j = m * HU + u;
     float* dg = sm;
     float* part = sm + H4;
-    lstm_u64* rg = ring + (size_t)(b * a.ndir + dir) * 2 * H4;
+    u64* rg = ring + (size_t)(b * a.ndir + dir) * 2 * H4;
     const bool owner = ks == 0;
     const int len = a.lengths ? a.lengths[b] : a.T;
     const size_t gstride = (size_t)a.ndir * H4, cstride = (size_t)a.ndir * H;
@@ -995,7 +939,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_split_res_kernel(LstmSplitArgs s
     for (int st = len - 1; st >= 0; --st) {
         const int tpos = dir == 0 ? st : (len - 1 - st);
         const unsigned tag = (unsigned)(len - st);
-        lstm_u64* slot = rg + (size_t)(st & 1) * H4;
+        u64* slot = rg + (size_t)(st & 1) * H4;
         if (owner) {
             const float ig = pg[0], fg = pg[1], gg = pg[2], og = pg[3];
             const float dh = pdy + dh_rec;
@@ -1007,11 +951,11 @@ __global__ __launch_bounds__(512) void lstm_bwd_split_res_kernel(LstmSplitArgs s
             const float d_f = dc * pcp * fg * (1.f - fg);
             dc_next = dc * fg;
             if (st > 0) {   // hand-off first: the other members are waiting for these four values
-                const lstm_u64 tg = (lstm_u64)tag << 32;
-                __hip_atomic_store(slot + j, tg | (lstm_u64)__float_as_uint(d_i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(slot + H + j, tg | (lstm_u64)__float_as_uint(d_f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(slot + 2 * H + j, tg | (lstm_u64)__float_as_uint(d_g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(slot + 3 * H + j, tg | (lstm_u64)__float_as_uint(d_o), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const u64 tg = granule_tag(tag);
+                st_granule_word(slot + j, d_i, tg);
+                st_granule_word(slot + H + j, d_f, tg);
+                st_granule_word(slot + 2 * H + j, d_g, tg);
+                st_granule_word(slot + 3 * H + j, d_o, tg);
             }
             float* p = dgrow + (size_t)tpos * gstride + j;   // (read by the weight-gradient GEMMs after this kernel)
             p[0] = d_i;
@@ -1030,7 +974,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_split_res_kernel(LstmSplitArgs s
                 off[r] = i0 + r * 512;
                 mask |= off[r] < H4 ? 1u << r : 0u;
             }
-            fail = !lstm_poll_n<4>(slot, off, off, mask, tag, s.abort_word, dg) || fail;
+            fail = !poll_granules_to<GS_SPIN_LIMIT, true>(slot, off, off, mask, tag, s.abort_word, dg) || fail;
         }
         if (__syncthreads_or(fail)) return;
         float x = 0.f;
@@ -1119,7 +1063,7 @@ static int lstm_split_members(int B, int ndir, int H) {
 // counters, this launch's abort word and (zero_ring) the granule ring restart at zero — ONE small launch.  Two hipMemsetAsync calls were THREE
 // fill kernels per recurrence launch (the runtime splits the 32 772-byte counter block into an aligned part and a 4-byte tail): at B = 1 that is 14 us
 // of a 150 us layer, eight layers per sentence (profiles/r06_e2e_single_sentence_launches.txt)
-__global__ __launch_bounds__(256) void lstm_rearm_kernel(unsigned* __restrict__ words, unsigned nwords, lstm_u64* __restrict__ ring, size_t n64) {
+__global__ __launch_bounds__(256) void lstm_rearm_kernel(unsigned* __restrict__ words, unsigned nwords, u64* __restrict__ ring, size_t n64) {
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nwords; i += stride) words[i] = 0u;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n64; i += stride) ring[i] = 0ull;
@@ -1134,10 +1078,10 @@ static HandoffArea* lstm_area(hipStream_t s, size_t ring_bytes, bool zero_ring =
         if (zero_ring && ring_bytes && hipMemsetAsync(ar->buf, 0, ring_bytes, s) != hipSuccess) return nullptr;
         return ar;
     }
-    const size_t n64 = zero_ring ? ring_bytes / sizeof(lstm_u64) : 0;
+    const size_t n64 = zero_ring ? ring_bytes / sizeof(u64) : 0;
     const size_t work = std::max<size_t>(ar->nwords + 1, n64);
     const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((work + 2047) / 2048, 1), 2048);
-    hipLaunchKernelGGL(lstm_rearm_kernel, dim3(blocks), dim3(256), 0, s, ar->words, (unsigned)(ar->nwords + 1), reinterpret_cast<lstm_u64*>(ar->buf), n64);
+    hipLaunchKernelGGL(lstm_rearm_kernel, dim3(blocks), dim3(256), 0, s, ar->words, (unsigned)(ar->nwords + 1), reinterpret_cast<u64*>(ar->buf), n64);
     if (hipGetLastError() != hipSuccess) return nullptr;
     return ar;
 }
@@ -1277,12 +1221,12 @@ extern "C" int ttsc_lstm_seq_backward(const float* dy_dev, const float* gates_de
         sa.KS = 512 / sa.HU;
         const size_t lds = ((size_t)4 * H + (size_t)sa.KS * sa.HU) * sizeof(float);
         if (path.id == TTSC_LSTM_PATH_SPLIT_RES) {   // H = 256 over 4 members: 128 rows of W_hh^T per thread stay in registers, granule hand-off
-            const size_t ring_bytes = (size_t)B * ndir * 2 * 4 * H * sizeof(lstm_u64);
+            const size_t ring_bytes = (size_t)B * ndir * 2 * 4 * H * sizeof(u64);
             HandoffArea* ar2 = lstm_area((hipStream_t)stream, ring_bytes, true);
             TTSC_REQUIRE(ar2, "ttsc_lstm_seq_backward: cannot allocate the hand-off ring");
             sa.cnt = ar2->words;
             sa.abort_word = ar2->abort_word();
-            lstm_u64* ring = reinterpret_cast<lstm_u64*>(ar2->buf);
+            u64* ring = reinterpret_cast<u64*>(ar2->buf);
             hipLaunchKernelGGL(lstm_bwd_split_res_kernel<128>, dim3((unsigned)G, (unsigned)B, (unsigned)ndir), dim3(512), lds, (hipStream_t)stream, sa, ring);
         } else {
             HandoffArea* ar = lstm_area((hipStream_t)stream, 0);
@@ -1345,12 +1289,12 @@ static int lstm_forward_impl(const float* xg_dev, const float* whh_packed_dev, f
         const int Gm = path.G, NB = path.NB, cap = path.cap;
         const int pairs = B * ndir, groups = ((B + NB - 1) / NB) * ndir;
         // granule ring [pairs][2 slots][H]: sized for this launch, grown on demand, one per (device, stream)
-        HandoffArea* ar = lstm_area((hipStream_t)stream, (size_t)pairs * 2 * H * sizeof(lstm_u64), true);
+        HandoffArea* ar = lstm_area((hipStream_t)stream, (size_t)pairs * 2 * H * sizeof(u64), true);
         if (!ar) {
             set_error("ttsc_lstm_seq_forward: cannot allocate the hand-off counters / ring");
             return TTSC_ENOMEM;
         }
-        lstm_u64* ring = reinterpret_cast<lstm_u64*>(ar->buf);
+        u64* ring = reinterpret_cast<u64*>(ar->buf);
         LstmSplitArgs sa{};
         sa.f = a;
         sa.cnt = ar->words;

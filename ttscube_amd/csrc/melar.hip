@@ -12,6 +12,7 @@
 // Dropout masks: injected ({0,1} floats, parity tests) or drawn in-kernel from Philox-4x32-10 counters (step, layer, unit).
 #include "common.hpp"
 #include "../../include/ttscube_math.h"
+#include "handoff.hpp"
 #include "rnn_chain.hpp"
 
 namespace ttsc {
@@ -36,48 +37,6 @@ struct MelArArgs {
     float init_mel;       // -5
     unsigned long long seed;
 };
-
-template <int NG, int UN>
-__device__ __forceinline__ void ar_chain(float (&acc)[NG], const float* __restrict__ wp, int rows, int gstride, int row,
-                                         const float* v, int K) {
-    // The lane's row index is made opaque at every call: the persistent kernels call this inside their time-step loop with the same
-    // weights every step, so all UN x NG load addresses are loop-invariant — hoisted out of the step loop they are 64-bit per-lane
-    // values that do not fit the register file (round-3 review: up to 225 VGPRs in scratch, each reload a dependent
-    // scratch_load -> global_load pair inside the step).  Recomputing them per call is two VALU instructions per load.
-    asm volatile("" : "+v"(row));
-    const float4* w4 = reinterpret_cast<const float4*>(wp) + row;
-    const int KB = K >> 2;
-    auto load = [&](float4 (&w)[UN][NG], int kb0) {
-#pragma unroll
-        for (int q = 0; q < UN; ++q)
-#pragma unroll
-            for (int g = 0; g < NG; ++g) w[q][g] = w4[(size_t)(kb0 + q) * rows + g * gstride];
-    };
-    auto fma_batch = [&](const float4 (&w)[UN][NG], int kb0) {
-#pragma unroll
-        for (int q = 0; q < UN; ++q) {
-            const float4 hv = *reinterpret_cast<const float4*>(v + 4 * (kb0 + q));
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                float x = acc[g];
-                x = fmaf(w[q][g].x, hv.x, x);
-                x = fmaf(w[q][g].y, hv.y, x);
-                x = fmaf(w[q][g].z, hv.z, x);
-                x = fmaf(w[q][g].w, hv.w, x);
-                acc[g] = x;
-            }
-        }
-    };
-    float4 wa[UN][NG], wb[UN][NG];
-    const int NB = KB / UN;  // caller guarantees KB % UN == 0
-    load(wa, 0);
-    for (int bi = 0; bi < NB; bi += 2) {
-        if (bi + 1 < NB) load(wb, (bi + 1) * UN);
-        fma_batch(wa, bi * UN);
-        if (bi + 2 < NB) load(wa, (bi + 2) * UN);
-        if (bi + 1 < NB) fma_batch(wb, (bi + 1) * UN);
-    }
-}
 
 __global__ __launch_bounds__(512) void melar_kernel(MelArArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -105,49 +64,49 @@ __global__ __launch_bounds__(512) void melar_kernel(MelArArgs a) {
         };
         // ---- PreNet layer 1: relu(W1 . last_mel + b1) * mask * 2 ----
         if (tid < P) {
-            float acc[1] = {a.b_pn1[tid]};
-            ar_chain<1, 5>(acc, a.w_pn1, P, 0, tid, lm, M);   // M = 80 -> 20 k-blocks
-            p1[tid] = fmaxf(acc[0], 0.f) * (mask(0, tid) * 2.f);
+            float acc[1][1] = {{a.b_pn1[tid]}};
+            lstm_chain<1, 1, 5>(acc, a.w_pn1, P, 0, tid, lm, 0, M);   // M = 80 -> 20 k-blocks
+            p1[tid] = fmaxf(acc[0][0], 0.f) * (mask(0, tid) * 2.f);
         }
         __syncthreads();
         // ---- PreNet layer 2 ----
         if (tid < P) {
-            float acc[1] = {a.b_pn2[tid]};
-            ar_chain<1, 8>(acc, a.w_pn2, P, 0, tid, p1, P);
-            p2[tid] = fmaxf(acc[0], 0.f) * (mask(1, tid) * 2.f);
+            float acc[1][1] = {{a.b_pn2[tid]}};
+            lstm_chain<1, 1, 8>(acc, a.w_pn2, P, 0, tid, p1, 0, P);
+            p2[tid] = fmaxf(acc[0][0], 0.f) * (mask(1, tid) * 2.f);
         }
         __syncthreads();
         // ---- LSTM layer 1: gates = xg1[t] + W_ih1[:, prenet part] . p2 + W_hh1 . h1 ----
         if (tid < H) {
-            float acc[4];
+            float acc[1][4];
             const float* xr = a.xg1 + ((size_t)b * a.S + t) * H4 + tid;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) acc[g] = xr[g * H];
-            ar_chain<4, 2>(acc, a.w_p2l, H4, H, tid, p2, P);
-            ar_chain<4, 2>(acc, a.w_hh1, H4, H, tid, h1 + cur * H, H);
-            const float ig = ttsc_sigmoidf(acc[0]), fg = ttsc_sigmoidf(acc[1]), gg = ttsc_tanhf(acc[2]), og = ttsc_sigmoidf(acc[3]);
+            for (int g = 0; g < 4; ++g) acc[0][g] = xr[g * H];
+            lstm_chain<1, 4, 2>(acc, a.w_p2l, H4, H, tid, p2, 0, P);
+            lstm_chain<1, 4, 2>(acc, a.w_hh1, H4, H, tid, h1 + cur * H, 0, H);
+            const float ig = ttsc_sigmoidf(acc[0][0]), fg = ttsc_sigmoidf(acc[0][1]), gg = ttsc_tanhf(acc[0][2]), og = ttsc_sigmoidf(acc[0][3]);
             c1 = fmaf(fg, c1, ig * gg);
             h1[nxt * H + tid] = og * ttsc_tanhf(c1);
         }
         __syncthreads();
         // ---- LSTM layer 2 ----
         if (tid < H) {
-            float acc[4];
+            float acc[1][4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) acc[g] = a.b2[g * H + tid];
-            ar_chain<4, 2>(acc, a.w_ih2, H4, H, tid, h1 + nxt * H, H);
-            ar_chain<4, 2>(acc, a.w_hh2, H4, H, tid, h2 + cur * H, H);
-            const float ig = ttsc_sigmoidf(acc[0]), fg = ttsc_sigmoidf(acc[1]), gg = ttsc_tanhf(acc[2]), og = ttsc_sigmoidf(acc[3]);
+            for (int g = 0; g < 4; ++g) acc[0][g] = a.b2[g * H + tid];
+            lstm_chain<1, 4, 2>(acc, a.w_ih2, H4, H, tid, h1 + nxt * H, 0, H);
+            lstm_chain<1, 4, 2>(acc, a.w_hh2, H4, H, tid, h2 + cur * H, 0, H);
+            const float ig = ttsc_sigmoidf(acc[0][0]), fg = ttsc_sigmoidf(acc[0][1]), gg = ttsc_tanhf(acc[0][2]), og = ttsc_sigmoidf(acc[0][3]);
             c2 = fmaf(fg, c2, ig * gg);
             h2[nxt * H + tid] = og * ttsc_tanhf(c2);
         }
         __syncthreads();
         // ---- output Linear H -> O (three frames); the last M values are fed back ----
         if (tid < O) {
-            float acc[1] = {a.b_out[tid]};
-            ar_chain<1, 8>(acc, a.w_out, O, 0, tid, h2 + nxt * H, H);
-            a.y[((size_t)b * a.S + t) * O + tid] = acc[0];
-            if (tid >= O - M) lm[tid - (O - M)] = acc[0];
+            float acc[1][1] = {{a.b_out[tid]}};
+            lstm_chain<1, 1, 8>(acc, a.w_out, O, 0, tid, h2 + nxt * H, 0, H);
+            a.y[((size_t)b * a.S + t) * O + tid] = acc[0][0];
+            if (tid >= O - M) lm[tid - (O - M)] = acc[0][0];
         }
         __syncthreads();
         cur = nxt;
@@ -220,15 +179,15 @@ __global__ __launch_bounds__(512) void melar_split_kernel(MelArSplitArgs s) {
         }
         // ---- PreNet (every member, identical arithmetic to melar_kernel) ----
         if (tid < P) {
-            float acc[1] = {a.b_pn1[tid]};
-            ar_chain<1, 5>(acc, a.w_pn1, P, 0, tid, lm, M);
-            p1[tid] = fmaxf(acc[0], 0.f) * (mask(0, tid) * 2.f);
+            float acc[1][1] = {{a.b_pn1[tid]}};
+            lstm_chain<1, 1, 5>(acc, a.w_pn1, P, 0, tid, lm, 0, M);
+            p1[tid] = fmaxf(acc[0][0], 0.f) * (mask(0, tid) * 2.f);
         }
         __syncthreads();
         if (tid < P) {
-            float acc[1] = {a.b_pn2[tid]};
-            ar_chain<1, 8>(acc, a.w_pn2, P, 0, tid, p1, P);
-            p2[tid] = fmaxf(acc[0], 0.f) * (mask(1, tid) * 2.f);
+            float acc[1][1] = {{a.b_pn2[tid]}};
+            lstm_chain<1, 1, 8>(acc, a.w_pn2, P, 0, tid, p1, 0, P);
+            p2[tid] = fmaxf(acc[0][0], 0.f) * (mask(1, tid) * 2.f);
         }
         __syncthreads();
         // ---- LSTM layer 1, this member's units: partial sums over the k-slices of p2 and h1_{t-1} ----
@@ -279,10 +238,10 @@ __global__ __launch_bounds__(512) void melar_split_kernel(MelArSplitArgs s) {
         __syncthreads();
         // ---- output Linear H -> O (every member; member 0 stores); the last M values are fed back ----
         if (tid < O) {
-            float acc[1] = {a.b_out[tid]};
-            ar_chain<1, 8>(acc, a.w_out, O, 0, tid, h2, H);
-            if (m == 0) a.y[((size_t)b * a.S + t) * O + tid] = acc[0];
-            if (tid >= O - M) lm[tid - (O - M)] = acc[0];
+            float acc[1][1] = {{a.b_out[tid]}};
+            lstm_chain<1, 1, 8>(acc, a.w_out, O, 0, tid, h2, 0, H);
+            if (m == 0) a.y[((size_t)b * a.S + t) * O + tid] = acc[0][0];
+            if (tid >= O - M) lm[tid - (O - M)] = acc[0][0];
         }
         __syncthreads();
     }
@@ -300,22 +259,6 @@ struct ttsc_melar {
     float *w_p2l = nullptr, *w_hh1 = nullptr, *w_ih2 = nullptr, *w_hh2 = nullptr, *b2 = nullptr, *w_out = nullptr, *b_out = nullptr;
     float *w_pn1 = nullptr, *b_pn1 = nullptr, *w_pn2 = nullptr, *b_pn2 = nullptr;
 };
-
-static int up(float** dst, const float* host, size_t n) {
-    if (*dst) (void)hipFree(*dst);
-    *dst = nullptr;
-    TTSC_HIP_CHECK(hipMalloc((void**)dst, n * sizeof(float)));
-    TTSC_HIP_CHECK(hipMemcpy(*dst, host, n * sizeof(float), hipMemcpyHostToDevice));
-    return TTSC_OK;
-}
-
-// host [rows, ld] (columns c0 .. c0+K) -> device [K/4][rows][4]
-static int up_packed4(float** dst, const float* host, int64_t rows, int64_t ld, int64_t c0, int64_t K) {
-    std::vector<float> t((size_t)rows * K);
-    for (int64_t r = 0; r < rows; ++r)
-        for (int64_t k = 0; k < K; ++k) t[((size_t)(k >> 2) * rows + r) * 4 + (k & 3)] = host[(size_t)r * ld + c0 + k];
-    return up(dst, t.data(), t.size());
-}
 
 extern "C" int ttsc_melar_create(int32_t H, int32_t P, int32_t M, int32_t O, ttsc_melar** out) {
     TTSC_REQUIRE(out, "ttsc_melar_create: null argument");
@@ -346,19 +289,19 @@ extern "C" int ttsc_melar_set_weights(ttsc_melar* m, const float* w_ih1, int64_t
     TTSC_REQUIRE(ld1 >= m->P, "ttsc_melar_set_weights: w_ih1 row length < prenet size");
     const int H = m->H, P = m->P;
     int rc;
-    if ((rc = up_packed4(&m->w_p2l, w_ih1, 4 * H, ld1, ld1 - P, P))) return rc;
-    if ((rc = up_packed4(&m->w_hh1, w_hh1, 4 * H, H, 0, H))) return rc;
-    if ((rc = up_packed4(&m->w_ih2, w_ih2, 4 * H, H, 0, H))) return rc;
-    if ((rc = up_packed4(&m->w_hh2, w_hh2, 4 * H, H, 0, H))) return rc;
+    if ((rc = upload_packed4(&m->w_p2l, w_ih1, 4 * H, ld1, ld1 - P, P))) return rc;
+    if ((rc = upload_packed4(&m->w_hh1, w_hh1, 4 * H, H, 0, H))) return rc;
+    if ((rc = upload_packed4(&m->w_ih2, w_ih2, 4 * H, H, 0, H))) return rc;
+    if ((rc = upload_packed4(&m->w_hh2, w_hh2, 4 * H, H, 0, H))) return rc;
     std::vector<float> b(4 * H);
     for (int i = 0; i < 4 * H; ++i) b[i] = b_ih2[i] + b_hh2[i];
-    if ((rc = up(&m->b2, b.data(), b.size()))) return rc;
-    if ((rc = up_packed4(&m->w_out, w_out, m->O, H, 0, H))) return rc;
-    if ((rc = up(&m->b_out, b_out, m->O))) return rc;
-    if ((rc = up_packed4(&m->w_pn1, pn_w1, P, m->M, 0, m->M))) return rc;
-    if ((rc = up(&m->b_pn1, pn_b1, P))) return rc;
-    if ((rc = up_packed4(&m->w_pn2, pn_w2, P, P, 0, P))) return rc;
-    return up(&m->b_pn2, pn_b2, P);
+    if ((rc = upload(&m->b2, b.data(), b.size()))) return rc;
+    if ((rc = upload_packed4(&m->w_out, w_out, m->O, H, 0, H))) return rc;
+    if ((rc = upload(&m->b_out, b_out, m->O))) return rc;
+    if ((rc = upload_packed4(&m->w_pn1, pn_w1, P, m->M, 0, m->M))) return rc;
+    if ((rc = upload(&m->b_pn1, pn_b1, P))) return rc;
+    if ((rc = upload_packed4(&m->w_pn2, pn_w2, P, P, 0, P))) return rc;
+    return upload(&m->b_pn2, pn_b2, P);
 }
 
 

@@ -183,6 +183,21 @@ int handoff_collect_stream(hipStream_t stream, unsigned* dst, int flags) {
     hipLaunchKernelGGL(status_collect_kernel, dim3(1), dim3(64), 0, stream, a);
     return hipGetLastError() == hipSuccess ? a.n : -1;
 }
+
+int upload(float** dst, const float* host, size_t n) {
+    if (*dst) (void)hipFree(*dst);
+    *dst = nullptr;
+    TTSC_HIP_CHECK(hipMalloc((void**)dst, n * sizeof(float)));
+    TTSC_HIP_CHECK(hipMemcpy(*dst, host, n * sizeof(float), hipMemcpyHostToDevice));
+    return TTSC_OK;
+}
+
+int upload_packed4(float** dst, const float* host, int64_t rows, int64_t ld, int64_t c0, int64_t K) {
+    std::vector<float> t((size_t)rows * K);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t k = 0; k < K; ++k) t[((size_t)(k >> 2) * rows + r) * 4 + (k & 3)] = host[(size_t)r * ld + c0 + k];
+    return upload(dst, t.data(), t.size());
+}
 }  // namespace ttsc
 
 // Device-side form of ttsc_split_status_stream: ONE launch on `stream` that ORs the verdict bits (1 LSTM | 2 GRU | 4 mel-AR | 8 other; 16 = the

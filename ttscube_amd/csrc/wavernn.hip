@@ -101,75 +101,6 @@ __global__ __launch_bounds__(256) void wr_cond_kernel(const float* __restrict__ 
     }
 }
 
-// acc[u][g] <- k-ordered fmaf chain over K inputs for NG rows (row g at rows-offset g*gstride + row) of a weight matrix
-// packed as [K/4][rows][4] (four consecutive k of one row are one 16-byte load; consecutive threads = consecutive rows, so
-// a wave reads 1 KiB contiguous per load).  v: LDS vector(s) [BT][vstride], read as 16-byte broadcasts.
-template <int BT, int NG, int UN>
-__device__ __forceinline__ void chain_matvec(float (&acc)[BT][NG], const float* __restrict__ wp, int rows, int gstride, int row,
-                                             const float* v, int vstride, int K) {
-    // Weight stream with EXPLICIT software pipelining: the 16-byte loads of a whole batch (UN k-blocks x NG rows) are
-    // issued back to back into one register set while the fmaf chain consumes the other set.  Left to itself hipcc
-    // places each load right before its use and waits vmcnt(0) per load, i.e. one L2 round trip per 16 bytes.
-    // The chain order (k ascending, one fmaf per term) is unchanged.
-    asm volatile("" : "+v"(row));   // (keeps the UN x NG load addresses from being hoisted out of the caller's step loop as 64-bit per-lane values: see rnn_chain.hpp)
-    const float4* w4 = reinterpret_cast<const float4*>(wp) + row;
-    const int KB = K >> 2;
-    auto load = [&](float4 (&w)[UN][NG], int kb0) {
-#pragma unroll
-        for (int q = 0; q < UN; ++q)
-#pragma unroll
-            for (int g = 0; g < NG; ++g) w[q][g] = w4[(size_t)(kb0 + q) * rows + g * gstride];
-    };
-    auto fma_batch = [&](const float4 (&w)[UN][NG], int kb0) {
-#pragma unroll
-        for (int q = 0; q < UN; ++q) {
-#pragma unroll
-            for (int u = 0; u < BT; ++u) {
-                const float4 hv = *reinterpret_cast<const float4*>(v + u * vstride + 4 * (kb0 + q));
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    float x = acc[u][g];
-                    x = fmaf(w[q][g].x, hv.x, x);
-                    x = fmaf(w[q][g].y, hv.y, x);
-                    x = fmaf(w[q][g].z, hv.z, x);
-                    x = fmaf(w[q][g].w, hv.w, x);
-                    acc[u][g] = x;
-                }
-            }
-        }
-    };
-    if (KB % UN == 0) {
-        float4 wa[UN][NG], wb[UN][NG];
-        const int NB = KB / UN;
-        load(wa, 0);
-        for (int bi = 0; bi < NB; bi += 2) {
-            if (bi + 1 < NB) load(wb, (bi + 1) * UN);
-            fma_batch(wa, bi * UN);
-            if (bi + 2 < NB) load(wa, (bi + 2) * UN);
-            if (bi + 1 < NB) fma_batch(wb, (bi + 1) * UN);
-        }
-    } else {
-        for (int kb = 0; kb < KB; ++kb) {
-            float4 w[NG];
-#pragma unroll
-            for (int g = 0; g < NG; ++g) w[g] = w4[(size_t)kb * rows + g * gstride];
-#pragma unroll
-            for (int u = 0; u < BT; ++u) {
-                const float4 hv = *reinterpret_cast<const float4*>(v + u * vstride + 4 * kb);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    float x = acc[u][g];
-                    x = fmaf(w[g].x, hv.x, x);
-                    x = fmaf(w[g].y, hv.y, x);
-                    x = fmaf(w[g].z, hv.z, x);
-                    x = fmaf(w[g].w, hv.w, x);
-                    acc[u][g] = x;
-                }
-            }
-        }
-    }
-}
-
 // The two output Linears (pre-output H -> 256, output 256 -> S): FOUR k-ordered chains over consecutive quarters of the inputs (in blocks of 4:
 // quarter q = blocks [q KB / 4, (q + 1) KB / 4)), the first seeded with the bias, added as ((p0 + p1) + p2) + p3 — the contract of
 // oracle/wavernn_ref.c::matvec_chain4, which the tile kernel (wavernn_tile.hip) evaluates with the four quarters on four waves.
@@ -180,7 +111,7 @@ __device__ __forceinline__ float chain_matvec_quarters(const float* __restrict__
     for (int q = 0; q < 4; ++q) {
         const int b0 = (q * KB) >> 2, b1 = ((q + 1) * KB) >> 2;
         float acc[1][1] = {{q == 0 ? bias : 0.f}};
-        chain_matvec<1, 1, 4>(acc, wp + (size_t)b0 * rows * 4, rows, 0, row, v + 4 * b0, 0, 4 * (b1 - b0));
+        lstm_chain<1, 1, 4>(acc, wp + (size_t)b0 * rows * 4, rows, 0, row, v + 4 * b0, 0, 4 * (b1 - b0));
         tot = q == 0 ? acc[0][0] : tot + acc[0][0];
     }
     return tot;
@@ -309,13 +240,13 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
                     for (int u = 0; u < BT; ++u)
 #pragma unroll
                         for (int g = 0; g < 3; ++g) gi[u][g] = a.b_ih[l][g * H + j];
-                    chain_matvec<BT, 3, 2>(gi, a.wt_ih[l], H3, H, j, hp, H, H);
+                    lstm_chain<BT, 3, 2>(gi, a.wt_ih[l], H3, H, j, hp, H, H);
                 }
 #pragma unroll
                 for (int u = 0; u < BT; ++u)
 #pragma unroll
                     for (int g = 0; g < 3; ++g) gh[u][g] = a.b_hh[l][g * H + j];
-                chain_matvec<BT, 3, 2>(gh, a.wt_hh[l], H3, H, j, hc, H, H);
+                lstm_chain<BT, 3, 2>(gh, a.wt_hh[l], H3, H, j, hc, H, H);
 #pragma unroll
                 for (int u = 0; u < BT; ++u) {
                     const float r = ttsc_sigmoidf(gi[u][0] + gh[u][0]);
@@ -457,22 +388,6 @@ struct ttsc_wavernn {
         return false;
     }
 };
-
-static int upload(float** dst, const float* host, size_t n) {
-    if (*dst) (void)hipFree(*dst);
-    *dst = nullptr;
-    TTSC_HIP_CHECK(hipMalloc((void**)dst, n * sizeof(float)));
-    TTSC_HIP_CHECK(hipMemcpy(*dst, host, n * sizeof(float), hipMemcpyHostToDevice));
-    return TTSC_OK;
-}
-
-// torch [rows, K] -> device [K/4][rows][4]: thread `row` reads four consecutive k as one 16-byte load (K % 4 == 0)
-static int upload_packed4(float** dst, const float* host, int64_t rows, int64_t K) {
-    std::vector<float> t((size_t)rows * K);
-    for (int64_t r = 0; r < rows; ++r)
-        for (int64_t k = 0; k < K; ++k) t[((size_t)(k >> 2) * rows + r) * 4 + (k & 3)] = host[(size_t)r * K + k];
-    return upload(dst, t.data(), t.size());
-}
 
 // torch [rows, cols] -> device [cols][rows] so that consecutive threads (rows) read consecutive addresses
 static int upload_transposed(float** dst, const float* host, int64_t rows, int64_t cols) {

@@ -26,13 +26,10 @@
 //     waves 1..3  recurrent product of step t+1 (three 64-row blocks, two 4-utterance accumulators each)
 // and joins for the gate math of step t+1 and the h_{t+1} hand-off.
 //
-// Hand-offs.  Every exchanged value is an 8-byte granule {fp32 value, step tag} written with ONE agent-scope store; a
-// consumer lane polls the granules it needs until they carry the tag of the step (bounded spin, shared abort word).  No
-// separate flag or counter, no producer-side drain, no barrier on the consumer side beyond the one that publishes the staged
-// vector in LDS.  Buffers are double-buffered by step parity: a member overwrites the step-t granule only at step t+2, which
-// it cannot reach before every member has published step t+1, i.e. has consumed step t.  (tools/probes/handoff_probe.hip:
-// 0.75 us per hand-off with agent-scope accesses, same or different XCD; workgroup-scope accesses are NOT coherent across
-// CUs.)  Members of a tile are still placed on one XCD (blockIdx -> XCD is round-robin).
+// Hand-offs.  Every exchanged value travels as an 8-byte granule {fp32 value, step tag} that the consumer lanes poll: the granule protocol of
+// handoff.hpp, with WT_SPIN_LIMIT and the abort word of this launch only.  No barrier on the consumer side beyond the one that publishes the
+// staged vector in LDS.  Members of a tile are placed on one XCD (blockIdx -> XCD is round-robin).
+#include "handoff.hpp"
 #include "rnn_chain.hpp"
 #include "wavernn_sampler.hpp"
 
@@ -47,60 +44,7 @@ constexpr int WT_XCDS = 8;
 #ifndef WT_TAIL_PRIO
 #define WT_TAIL_PRIO 0   // issue priority of waves 4..7 while they run the output Linears.  Measured (profiles/r06_wavernn_phase_timeline.log): 2 shortens the tail (wave 0 waits 5.7 instead of 7.2 us) and lengthens the recurrent product behind it by more — 14.5 against 14.1 us per step: off
 #endif
-constexpr unsigned WT_SPIN_LIMIT = 1u << 20;   // bounded spins: a member that is not resident must not hang the GPU
-
-typedef unsigned long long u64;
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void st_granule(u64* p, float v, unsigned tag) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Poll N granules (p[i * stride]) until all carry `tag`; false after a timeout or when another member aborted.
-template <int N>
-__device__ __forceinline__ bool ld_granules(const u64* p, int stride, unsigned tag, float (&v)[N], unsigned* abort_word) {
-    u64 g[N];
-    unsigned spins = 0;
-    for (;;) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) g[i] = __hip_atomic_load(p + (size_t)i * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool all = true;
-#pragma unroll
-        for (int i = 0; i < N; ++i) all = all && ((unsigned)(g[i] >> 32) == tag);
-        if (all) break;
-        if (++spins > WT_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);   // (longer back-offs only add latency: measured 18.1 / 18.7 / 20.8 us per step for 0 / 1k / 4k clocks)
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = __uint_as_float((unsigned)g[i]);
-    return true;
-}
-
-// same, granules p[off[i]]
-template <int N>
-__device__ __forceinline__ bool ld_granules_at(const u64* p, const int (&off)[N], unsigned tag, float (&v)[N], unsigned* abort_word) {
-    u64 g[N];
-    unsigned spins = 0;
-    for (;;) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) g[i] = __hip_atomic_load(p + off[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool all = true;
-#pragma unroll
-        for (int i = 0; i < N; ++i) all = all && ((unsigned)(g[i] >> 32) == tag);
-        if (all) break;
-        if (++spins > WT_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);   // (longer back-offs only add latency: measured 18.1 / 18.7 / 20.8 us per step for 0 / 1k / 4k clocks)
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = __uint_as_float((unsigned)g[i]);
-    return true;
-}
 
 struct WtArgs {
     const float* mel;      // [B, T, n_mel]
@@ -557,7 +501,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
         {
             const u64* src = xpre + ((size_t)(s & 1) * 256 + 64 * q) * BU + lane;
             float v[8];
-            okq = ld_granules<8>(src, 64, (unsigned)s + 1u, v, a.abort_word) && okq;
+            okq = poll_granules_strided<WT_SPIN_LIMIT, false>(src, 64, (unsigned)s + 1u, a.abort_word, v) && okq;
             WT_TICKW(12);
 #pragma unroll
             for (int r = 0; r < 8; ++r) pvec[(lane & 7) * VP + 64 * q + r * 8 + (lane >> 3)] = v[r];
@@ -643,8 +587,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                     }
                 }
                 if (((lane & 31) >> 2) == 0)   // candidate granule {score, (tag << 8) | class}: xlog area, [parity][utterance][member]
-                    __hip_atomic_store(xlog + ((size_t)par * BU + tutt) * SP + m, ((u64)((tag << 8) | (unsigned)(bi & 255)) << 32) | (u64)__float_as_uint(best),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    st_granule(xlog + ((size_t)par * BU + tutt) * SP + m, best, (tag << 8) | (unsigned)(bi & 255));
             }
         }
         WT_TICK(6);
@@ -652,7 +595,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
           if (m < nu) {   // continuous heads (MOL / Gaussian / Beta): S <= 30 output values of utterance m
             const int bs = g * BU + m;
             float v[1] = {0.f};
-            if (lane < SP) ok = ld_granules<1>(xlog + ((size_t)par * BU + m) * SP + lane, 1, tag, v, a.abort_word) && ok;
+            if (lane < SP) ok = poll_granules_strided<WT_SPIN_LIMIT, false>(xlog + ((size_t)par * BU + m) * SP + lane, 1, tag, a.abort_word, v) && ok;
             if (lane < 32) ybuf[lane] = v[0];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -669,20 +612,11 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
         } else {   // discrete heads: every member reduces the 8 (members) x 8 (utterances) candidates; lane -> (utterance l >> 3, member l & 7)
             const int cu = lane >> 3, cm = lane & 7;
             const u64* src = xlog + ((size_t)par * BU + cu) * SP + cm;
-            u64 gq;
-            unsigned spins = 0;
-            for (;;) {
-                gq = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned)(gq >> 40) == (tag & 0xFFFFFFu)) break;
-                if (++spins > WT_SPIN_LIMIT || ((spins & 63u) == 0u && __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                    __hip_atomic_store(a.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = false;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            float best = __uint_as_float((unsigned)gq);
-            int bi = (int)((gq >> 32) & 255u);
+            u64 gq[1];
+            const int at[1] = {0};
+            ok = poll_granules<WT_SPIN_LIMIT, false, 40>(src, at, 1u, tag & 0xFFFFFFu, a.abort_word, gq) && ok;
+            float best = granule_value(gq[0]);
+            int bi = (int)((gq[0] >> 32) & 255u);
 #pragma unroll
             for (int off2 = 1; off2 <= 4; off2 <<= 1) {   // classes of a lower member are lower: "first maximum wins" = lower class on ties
                 const float os = __shfl_xor(best, off2);
@@ -771,7 +705,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
         if (gru_thr) {
             float lx[1] = {0.f};
             if constexpr (CONT) {
-                if (t > 0 && u < nu) ok = ld_granules<1>(xlx + (par ^ 1) * BU + u, 1, (unsigned)t, lx, a.abort_word);
+                if (t > 0 && u < nu) ok = poll_granules_strided<WT_SPIN_LIMIT, false>(xlx + (par ^ 1) * BU + u, 1, (unsigned)t, a.abort_word, lx);
             } else if (t > 0) {
                 lx[0] = lxv[u];   // written by wave 0 in the tail of step t-1, before the join barrier
             }
@@ -798,7 +732,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
             for (int i0 = tid; i0 < BU * H; i0 += 8 * WT_THREADS) {
                 if (i0 + 7 * WT_THREADS < BU * H) {   // H = 512: one round trip for the whole vector
                     float v[8];
-                    ok = ld_granules<8>(src + i0, WT_THREADS, (unsigned)t + 1u, v, a.abort_word) && ok;
+                    ok = poll_granules_strided<WT_SPIN_LIMIT, false>(src + i0, WT_THREADS, (unsigned)t + 1u, a.abort_word, v) && ok;
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
                         const int i = i0 + r * WT_THREADS;
@@ -807,7 +741,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                 } else {
                     for (int i = i0; i < BU * H; i += WT_THREADS) {
                         float v[1];
-                        ok = ld_granules<1>(src + i, 1, (unsigned)t + 1u, v, a.abort_word) && ok;
+                        ok = poll_granules_strided<WT_SPIN_LIMIT, false>(src + i, 1, (unsigned)t + 1u, a.abort_word, v) && ok;
                         hvec[(i & 7) * VH + (i >> 3)] = v[0];
                     }
                 }
@@ -840,7 +774,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                 for (int i0 = tid; i0 < BU * H; i0 += 8 * WT_THREADS) {
                     if (i0 + 7 * WT_THREADS < BU * H) {
                         float v[8];
-                        ok = ld_granules<8>(src + i0, WT_THREADS, (unsigned)t + 1u, v, a.abort_word) && ok;
+                        ok = poll_granules_strided<WT_SPIN_LIMIT, false>(src + i0, WT_THREADS, (unsigned)t + 1u, a.abort_word, v) && ok;
 #pragma unroll
                         for (int r = 0; r < 8; ++r) {
                             const int i = i0 + r * WT_THREADS;
@@ -849,7 +783,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                     } else {
                         for (int i = i0; i < BU * H; i += WT_THREADS) {
                             float v[1];
-                            ok = ld_granules<1>(src + i, 1, (unsigned)t + 1u, v, a.abort_word) && ok;
+                            ok = poll_granules_strided<WT_SPIN_LIMIT, false>(src + i, 1, (unsigned)t + 1u, a.abort_word, v) && ok;
                             hvec2[(i & 7) * VH + (i >> 3)] = v[0];
                         }
                     }
