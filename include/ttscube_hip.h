@@ -669,6 +669,30 @@ int ttsc_textcoder_loss(const float* dur_logits_dev, const int64_t* dur_target_d
                         int64_t n, int64_t ignore_index, float* out_dev, float* g_dur_dev, float* g_pitch_dev, float* g_pre_dev, float* g_post_dev,
                         int32_t* status_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* Sentence phonemizer (cube/networks/phonemizer.py:12-103 CubenetPhonemizer, cube/io_utils/io_text.py:13-61; csrc/phonemizer.hip).
+ *   ttsc_char_features   the tagger's input in one launch: out [B, Ec + Es, N] (channel-major, what ttsc_conv1d_forward reads) =
+ *                        cat[char_table[x_char], case_table[x_case]] permuted, zero at positions n >= len_dev[b] (len_dev NULL: none).  Tables are
+ *                        [G, Ec] and [Gc, Es]; an id outside its table writes zeros and sets bit 1 of the phonemizer status word.
+ *   ttsc_tag_argmax      tags[m] = index of the FIRST maximum of x[m, :K] . W[P, K]^T + bias (torch.argmax's rule; bias may be NULL), 0 for
+ *                        rows at or beyond their utterance's length (len_dev [M / period], rows are [utterance][period]; NULL: every row counts).
+ *                        logits_dev [M, P] may be NULL (the product path never writes them); padding rows get zeros there.  K % 4 == 0,
+ *                        ldx % 4 == 0, 16-byte aligned x / W, K + P <= 4096.  fp32 accumulation, k = 0 .. K-1 in order per (row, class): the
+ *                        result of a row does not depend on M or on the rows around it.
+ *   ttsc_masked_ce       *loss_dev = mean over the rows whose target != ignore_index of CE(logits[r, :K], target[r]) — 0 when there is no such
+ *                        row (torch gives NaN there) — and dlogits [R, K] = d loss / d logits (already divided by the row count; ignored rows
+ *                        zero).  Deterministic (fixed-order two-stage reduction).  A target outside [0, K) that is not ignore_index
+ *                        contributes nothing, sets bit 2 of the phonemizer status word and, when status_dev is given, *status_dev = 2 (else 0).
+ *                        Workspace: ttsc_masked_ce_workspace_bytes(R).
+ *   ttsc_phonemizer_status   the sticky per-device status word of the kernels above (bit 1 | bit 2), cleared by the read; synchronises. */
+int ttsc_char_features(const int32_t* x_char_dev, const int32_t* x_case_dev, const float* char_table_dev, const float* case_table_dev,
+                       const int32_t* len_dev, int32_t B, int32_t N, int32_t G, int32_t Ec, int32_t Gc, int32_t Es, float* out_dev, void* stream);
+int ttsc_tag_argmax(const float* x_dev, const float* w_dev, const float* bias_dev, const int32_t* len_dev, int32_t period, int64_t M, int32_t P,
+                    int32_t K, int64_t ldx, int32_t* tags_dev, float* logits_dev, void* stream);
+size_t ttsc_masked_ce_workspace_bytes(int32_t R);
+int ttsc_masked_ce(const float* logits_dev, const int64_t* target_dev, int32_t R, int32_t K, int64_t ignore_index, float* loss_dev,
+                   float* dlogits_dev, int32_t* status_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int32_t ttsc_phonemizer_status(void);
+
 #ifdef __cplusplus
 }
 #endif

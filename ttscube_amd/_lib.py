@@ -227,6 +227,12 @@ SIGNATURES = {
     'ttsc_textcoder_loss_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
     'ttsc_textcoder_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'ttsc_char_features': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
+    'ttsc_tag_argmax': (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttsc_masked_ce_workspace_bytes': (C.c_size_t, [C.c_int32]),
+    'ttsc_masked_ce': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    'ttsc_phonemizer_status': (C.c_int32, []),
 }
 
 

@@ -1,9 +1,10 @@
 """Mirror of cube/api.py: ``TTSCube.load(model_name)`` / ``TTSCube(model_path, phonemizer_path)`` /
 ``tts(text, speaker) -> np.int16 @ 24 kHz``.
 
-The text front-end (phonemizer network + tokenizers, cube/io_utils/io_text.py) is outside the hot path (SURVEY.md
-§2.1): pass ``text2feat`` = any callable ``text -> {'phones': [...], 'words': [...], 'phon2word': [...]}`` (the
-reference's Text2Feat* objects satisfy it); without one, the text is read as whitespace-separated phoneme symbols.
+The text front-end: when ``<phonemizer_path>.encodings`` and ``<phonemizer_path>.model`` exist, plain text is phonemized by
+``io_utils.io_text.Text2FeatBlizzard`` (the reference's tokenizer + character tagger, on the HIP kernels).  ``text2feat`` = any
+callable ``text -> {'phones': [...], 'words': [...], 'phon2word': [...]}`` overrides it (the reference's Text2Feat* objects
+satisfy it); with neither, the text is read as whitespace-separated phoneme symbols.
 New on top of the reference (B=1 only): ``synthesize_batch`` runs many sentences per call, length-bucketed, and
 ``shard`` splits a sentence list across ranks (one process per GPU, no collectives)."""
 import os
@@ -39,9 +40,19 @@ class TTSCube:
         self._model = Cubegan(encodings, conditioning=cond_type, train=False)
         self._model.load('{0}.model'.format(model_path))
         self._collate = CubeganCollate(encodings, conditioning_type=cond_type)
-        self._text2feat = text2feat if text2feat is not None else PhoneText2Feat()
         self._model.eval()
         self._model.to(device)
+        self._text2feat = self._make_text2feat(phonemizer_path, text2feat, device)
+
+    @staticmethod
+    def _make_text2feat(phonemizer_path, text2feat, device):
+        """the caller's front-end; else the phonemizer (cube/api.py:31-32) when both of its files exist; else the phoneme-string reader"""
+        if text2feat is not None:
+            return text2feat
+        if phonemizer_path is not None and all(os.path.exists('{0}.{1}'.format(phonemizer_path, ext)) for ext in ('encodings', 'model')):
+            from .io_utils.io_text import Text2FeatBlizzard
+            return Text2FeatBlizzard(phonemizer_path, device=device)
+        return PhoneText2Feat()
 
     @staticmethod
     def load(model_name: str, **kw):
@@ -51,9 +62,9 @@ class TTSCube:
                                     'download it (cube/io_utils/repository.py:27-61); unpack the exported model there' % base_name)
         return TTSCube('{0}/cubegan'.format(base_name), '{0}/phonemizer'.format(base_name), **kw)
 
-    def _example(self, text, speaker):
-        """The dummy-target example cube/api.py:47-57 builds around the front-end output."""
-        rez = {'meta': dict(self._text2feat(text))}
+    def _example(self, text, speaker, feats=None):
+        """The dummy-target example cube/api.py:47-57 builds around the front-end output (`feats`: that output, when the caller already has it)."""
+        rez = {'meta': dict(self._text2feat(text) if feats is None else feats)}
         rez['meta']['speaker'] = speaker
         rez['pitch'] = np.zeros((100))
         rez['mgc'] = np.zeros((100, 80))
@@ -91,7 +102,9 @@ class TTSCube:
         padded batches of up to `max_batch`; ragged lengths are handled inside the kernels (masked BiLSTMs), so each
         result equals the single-sentence call."""
         speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
-        ex = [self._example(t, s) for t, s in zip(texts, speakers)]
+        # a front-end with a `batch` method (io_text.Text2FeatBlizzard) phonemizes the whole list in one padded call
+        feats = self._text2feat.batch(list(texts)) if hasattr(self._text2feat, 'batch') else [None] * len(texts)
+        ex = [self._example(t, s, f) for t, s, f in zip(texts, speakers, feats)]
         order = sorted(range(len(ex)), key=lambda i: len(ex[i]['meta']['phones']))
         out = [None] * len(ex)
         groups = [order[s:s + max_batch] for s in range(0, len(order), max_batch)]
