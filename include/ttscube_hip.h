@@ -693,6 +693,50 @@ int ttsc_masked_ce(const float* logits_dev, const int64_t* target_dev, int32_t R
                    float* dlogits_dev, int32_t* status_dev, void* ws_dev, size_t ws_bytes, void* stream);
 int32_t ttsc_phonemizer_status(void);
 
+/* Word-level G2P (cube/networks/modules.py:58-88, 208-297 Seq2Seq + Attention in eval mode; cube/networks/g2p.py; csrc/g2p.hip).
+ *   ttsc_g2p_decode   the autoregressive attention decoder of Seq2Seq.forward as ONE launch, one workgroup per word and no communication between
+ *                     workgroups.  Per step: query = CELL state of the last decoder layer -> energy_n = tanh(W_att[:, :D] q + pe_n) ->
+ *                     attention = softmax over ALL n_b positions of v . energy_n (padding included, as the reference) -> context -> two LSTM
+ *                     layers -> logits = W_out h2 + b -> the fed-back label (first maximum of the logits, or gs[b, t]).  The start state is
+ *                     the state after one step on a zero input from a zero state; the first fed-back embedding is zero.
+ *                     The caller hoists pe = enc . W_att[:, D:]^T + b_att [B, Nmax, A] and tab = output_emb . W_ih0[:, E:]^T [L, 4D]
+ *                     (ttsc_linear_forward); matrices are packed [K/4][rows][4] (see ttsc_lstm_pack_whh), biases are b_ih + b_hh.
+ *                     n_dev [B]: the padded length of each word (1 .. Nmax; NULL: Nmax) — words of different batches share a launch and each
+ *                     sees the padding it would see alone.  A word's encoder rows stay in LDS while they fit (64 KiB), else they are read from
+ *                     global memory: no n is refused.  scratch_dev: 2 * B * Nmax floats.
+ *                     stop != 0: a word ends with its first label == eos, at the latest after min(T, 10 * n_b + 1) steps; else every word runs T
+ *                     steps.  idx_dev [B, T] int32 labels (0 beyond a word's steps), count_dev [B] steps run, logits_dev [B, T, L] (zeros beyond
+ *                     a word's steps); each may be NULL.  gs_dev [B, T] int32 teacher labels or NULL.  D, E, A multiples of 4.
+ *                     A teacher label outside [0, L) feeds back zeros and sets bit 2 of the G2P status word; an n_b outside [1, Nmax] is
+ *                     clamped and sets bit 4.
+ *   ttsc_g2p_embed    out [R, Em] = table[ids[r]] (table [G, Em]); an id outside the table writes zeros and sets bit 1 of the status word.
+ *   ttsc_g2p_status   the sticky per-device status word of the two (bits 1 | 2 | 4), cleared by the read; synchronises. */
+typedef struct ttsc_g2p_args {
+    const float* enc_dev;      /* [B, Nmax, E] encoder states */
+    const float* pe_dev;       /* [B, Nmax, A] */
+    const int32_t* n_dev;      /* [B] or NULL */
+    const int32_t* gs_dev;     /* [B, T] or NULL */
+    const float* w_aq;         /* W_att[:, :D] packed [D/4][A][4] */
+    const float* v;            /* [A] */
+    const float* w_ic;         /* W_ih0[:, :E] packed [E/4][4D][4] */
+    const float* tab;          /* [L, 4D] */
+    const float* w_hh0;        /* packed [D/4][4D][4] */
+    const float* b0;           /* [4D] */
+    const float* w_ih1;        /* packed [D/4][4D][4] */
+    const float* w_hh1;        /* packed [D/4][4D][4] */
+    const float* b1;           /* [4D] */
+    const float* w_out;        /* packed [D/4][L][4] */
+    const float* b_out;        /* [L] */
+    float* scratch_dev;        /* [2, B, Nmax] */
+    int32_t* idx_dev;          /* [B, T] or NULL */
+    int32_t* count_dev;        /* [B] or NULL */
+    float* logits_dev;         /* [B, T, L] or NULL */
+    int32_t B, Nmax, T, E, A, D, L, eos, stop;
+} ttsc_g2p_args;
+int ttsc_g2p_decode(const ttsc_g2p_args* args, void* stream);
+int ttsc_g2p_embed(const int32_t* ids_dev, const float* table_dev, int64_t R, int32_t G, int32_t Em, float* out_dev, void* stream);
+int32_t ttsc_g2p_status(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,13 @@ class WavernnCfg(C.Structure):
                 ('upsample_low', C.c_int32), ('S', C.c_int32), ('n_mel', C.c_int32), ('out_kind', C.c_int32)]
 
 
+class G2pArgs(C.Structure):
+    """ttsc_g2p_args (include/ttscube_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ('enc_dev', 'pe_dev', 'n_dev', 'gs_dev', 'w_aq', 'v', 'w_ic', 'tab', 'w_hh0', 'b0', 'w_ih1', 'w_hh1', 'b1',
+                                          'w_out', 'b_out', 'scratch_dev', 'idx_dev', 'count_dev', 'logits_dev')] + \
+               [(n, C.c_int32) for n in ('B', 'Nmax', 'T', 'E', 'A', 'D', 'L', 'eos', 'stop')]
+
+
 WR_OUT_MULAW, WR_OUT_RAW, WR_OUT_MOL, WR_OUT_GM, WR_OUT_BETA = 0, 1, 2, 3, 4
 WR_MODE_ARGMAX, WR_MODE_NOISE, WR_MODE_PHILOX = 0, 1, 2
 
@@ -233,6 +240,9 @@ SIGNATURES = {
     'ttsc_masked_ce': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
     'ttsc_phonemizer_status': (C.c_int32, []),
+    'ttsc_g2p_decode': (C.c_int, [C.POINTER(G2pArgs), C.c_void_p]),
+    'ttsc_g2p_embed': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'ttsc_g2p_status': (C.c_int32, []),
 }
 
 

@@ -2,7 +2,8 @@
 ``tts(text, speaker) -> np.int16 @ 24 kHz``.
 
 The text front-end: when ``<phonemizer_path>.encodings`` and ``<phonemizer_path>.model`` exist, plain text is phonemized by
-``io_utils.io_text.Text2FeatBlizzard`` (the reference's tokenizer + character tagger, on the HIP kernels).  ``text2feat`` = any
+``io_utils.io_text.Text2FeatBlizzard`` (the reference's tokenizer + character tagger, on the HIP kernels); when the files are a word-level G2P
+(JSON ``.encodings`` with ``token2int``, ``.best`` / ``.model`` and ``.lexicon``) by ``io_utils.io_text.Text2Feat``.  ``text2feat`` = any
 callable ``text -> {'phones': [...], 'words': [...], 'phon2word': [...]}`` overrides it (the reference's Text2Feat* objects
 satisfy it); with neither, the text is read as whitespace-separated phoneme symbols.
 New on top of the reference (B=1 only): ``synthesize_batch`` runs many sentences per call, length-bucketed, and
@@ -46,13 +47,40 @@ class TTSCube:
 
     @staticmethod
     def _make_text2feat(phonemizer_path, text2feat, device):
-        """the caller's front-end; else the phonemizer (cube/api.py:31-32) when both of its files exist; else the phoneme-string reader"""
+        """the caller's front-end; else the word-level G2P (Text2Feat) when phonemizer_path holds one; else the sentence phonemizer (cube/api.py:31-32)
+        when both of its files exist; else the phoneme-string reader"""
         if text2feat is not None:
             return text2feat
+        g2p = TTSCube._g2p_files(phonemizer_path) if phonemizer_path is not None else None
+        if g2p == 'complete':
+            from .io_utils.io_text import Text2Feat
+            return Text2Feat(phonemizer_path, device=device)
+        if g2p == 'incomplete':         # a G2P's encodings without its lexicon or checkpoint: never the sentence tagger's files
+            return PhoneText2Feat()
         if phonemizer_path is not None and all(os.path.exists('{0}.{1}'.format(phonemizer_path, ext)) for ext in ('encodings', 'model')):
             from .io_utils.io_text import Text2FeatBlizzard
             return Text2FeatBlizzard(phonemizer_path, device=device)
         return PhoneText2Feat()
+
+    @staticmethod
+    def _g2p_files(phonemizer_path):
+        """the word-level G2P's files (the reference's en-* layout, cube/api.py:26-29 second branch): a JSON .encodings with a `token2int` key —
+        the sentence tagger's has `grapheme2int` —, a .best or .model checkpoint and a .lexicon.
+        -> 'complete', 'incomplete' (such an .encodings, but the lexicon or the checkpoint is missing) or None (not a G2P's encodings)"""
+        import json
+        f = lambda ext: '{0}.{1}'.format(phonemizer_path, ext)
+        try:
+            with open(f('encodings')) as fh:
+                obj = json.load(fh)
+        except (OSError, ValueError):
+            return None
+        if not (isinstance(obj, dict) and 'token2int' in obj):
+            return None
+        return 'complete' if os.path.exists(f('lexicon')) and (os.path.exists(f('best')) or os.path.exists(f('model'))) else 'incomplete'
+
+    @staticmethod
+    def _is_g2p(phonemizer_path):
+        return TTSCube._g2p_files(phonemizer_path) == 'complete'
 
     @staticmethod
     def load(model_name: str, **kw):

@@ -1,10 +1,15 @@
-"""Mirror of cube/io_utils/io_text.py:13-61 and cube/networks/g2p.py:247-264: the runtime text front-end — plain text in, the
+"""Mirror of cube/io_utils/io_text.py:13-96 and cube/networks/g2p.py:247-264: the runtime text front-ends — plain text in, the
 {'orig_text', 'words', 'phones', 'phon2word'} dict the synthesis collate reads out.
 
     text -> '§' wrapping / newline rules -> SimpleTokenizer (words) -> CubenetPhonemizer.tag (one tag per character, on the HIP kernels)
          -> curation: '_' tags dropped, every kept phone mapped to the word its character lies in
 
-`batch(texts)` tags many sentences with one padded, length-aware `tag` call; each result equals the single call's."""
+`batch(texts)` tags many sentences with one padded, length-aware `tag` call; each result equals the single call's.
+
+``Text2Feat`` is the other front-end of the reference (io_text.py:64-96), for model directories whose phonemizer files are a word-level G2P:
+
+    text -> newline rules / space wrapping -> networks.g2p.G2P (tokenizer, lexicon, attention decoder on ttsc_g2p_decode, non-word rules)
+         -> '_' phones dropped, the empty-string phones of punctuation kept, every kept phone mapped to its token"""
 import numpy as np
 import torch
 
@@ -110,3 +115,57 @@ class Text2FeatBlizzard:
         if not texts:
             return []
         return [self._finish(t, tags) for t, tags in zip(texts, self._tags(texts))]
+
+
+def wrap_text(text):
+    """io_text.py:73-79: newlines become spaces; the sentence is wrapped in spaces"""
+    text = text.replace('\n\n', ' ').replace('\n', ' ')
+    if not text.startswith(' '):
+        text = ' ' + text
+    if not text[-1] == ' ':
+        text = text + ' '
+    return text
+
+
+def assemble(text, trace):
+    """io_text.py:82-96: trace = [{'word', 'transcription'}] per token -> the front-end dict ('_' dropped, '' kept, as the reference keeps them)"""
+    words, phones, phon2word = [], [], []
+    for i, tok in enumerate(trace):
+        words.append(tok['word'])
+        for ph in tok['transcription']:
+            if ph != '_':
+                phones.append(ph)
+                phon2word.append(i)
+    return {'orig_text': text, 'words': words, 'phones': phones, 'phon2word': phon2word}
+
+
+class Text2Feat:
+    def __init__(self, phonemizer_path: str, device='cuda:0'):
+        from ..networks.g2p import G2P
+        g2p = G2P()
+        g2p.load(phonemizer_path)
+        g2p.load_lexicon('{0}.lexicon'.format(phonemizer_path))
+        g2p.eval()
+        g2p.to(device)
+        self._phonemizer = g2p
+        self._tokenizer = SimpleTokenizer()
+
+    @classmethod
+    def from_g2p(cls, g2p):
+        """a front-end around an existing G2P object (its model already on its device)"""
+        self = cls.__new__(cls)
+        self._phonemizer = g2p
+        self._tokenizer = SimpleTokenizer()
+        return self
+
+    def __call__(self, text):
+        text = wrap_text(text)
+        _, trace = self._phonemizer(text, trace=True)
+        return assemble(text, trace)
+
+    def batch(self, texts):
+        """the words of all sentences in one decoder launch, each padded to its own sentence's N: every result equals the single call's"""
+        texts = [wrap_text(t) for t in texts]
+        if not texts:
+            return []
+        return [assemble(t, trace) for t, (_, trace) in zip(texts, self._phonemizer.batch(texts, trace=True))]

@@ -37,6 +37,14 @@ class ConvNorm(nn.Module):
         nn.init.xavier_normal_(self.conv.weight, gain=nn.init.calculate_gain(w_init_gain))
 
 
+def __getattr__(name):
+    """``Seq2Seq`` / ``Attention`` (cube/networks/modules.py:58-88, 208-314) live in networks/seq2seq.py and resolve here under the reference's names"""
+    if name in ('Seq2Seq', 'Attention'):
+        from . import seq2seq
+        return getattr(seq2seq, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
+
 def _param_signature(module):
     return tuple((p.data_ptr(), p._version) for p in module.parameters())
 
