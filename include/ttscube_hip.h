@@ -737,6 +737,68 @@ int ttsc_g2p_decode(const ttsc_g2p_args* args, void* stream);
 int ttsc_g2p_embed(const int32_t* ids_dev, const float* table_dev, int64_t R, int32_t G, int32_t Em, float* out_dev, void* stream);
 int32_t ttsc_g2p_status(void);
 
+/* G2P training (modules.py:258-297 Seq2Seq.forward with gs_output in TRAIN mode; csrc/g2p_train.hip).  One workgroup per word, nothing between
+ * workgroups.  Row r = 0 of every saved tensor is the start step (zero input, zero state), row r = t + 1 is teacher-forced step t.
+ *   ttsc_g2p_train_forward    the start step and all T steps in one launch.  Per step: aq = W_att[:, :D] . c2 (CELL state of the top layer),
+ *                             energy = keep_att * tanh(aq + pe_i) / (1 - p_att), attention = softmax over ALL N positions of v . energy, context,
+ *                             layer 0 on [context; output_emb(y[t - 1])] (zero embedding at t = 0; the embedding enters as tab = output_emb .
+ *                             W_ih0[:, E:]^T), keep_dec / (1 - p_dec) on layer 0's h towards layer 1 (a fresh mask every row, the start step
+ *                             included), layer 1.  Saves activated gates (i, f, g, o) and cell states of both layers, h1, the masked h1, h2, aq,
+ *                             the attention weights and the contexts (into columns [0, E) of the decoder-input rows x0 [B, T + 1, E + Em], whose
+ *                             other entries the caller fills).  The energies are not stored: the backward recomputes them from aq.  No logits:
+ *                             under teacher forcing they are one GEMM over the rows of h2.
+ *   ttsc_g2p_train_backward   the reverse loop in one launch from dh2 [B, T, D]: gate gradients of both layers for all T + 1 rows (the rows of
+ *                             the weight-gradient GEMMs), dq [B, T + 1, A] (row 0 untouched: the caller zeroes it), and per word denc [B, N, E]
+ *                             (through the context only), dpe [B, N, A] and dv [B, A], accumulated over t descending by the owning thread: no
+ *                             atomics, the same bits every run.  Streams [W_ih1^T; W_hh1^T], [W_hh0^T; W_ic^T] and W_aq^T in the forward packing.
+ *   Masks: {0,1} floats, or NULL = Philox-4x32-10, counter (element >> 2, row, word, tag + stream_id), key = seed (p = 0: everything kept).
+ *   A label outside [0, L) feeds zeros and sets bit 2 of the G2P status word (ttsc_g2p_status).  D, E, A multiples of 4.
+ *   ttsc_dropout_scale        y[i] = x[i] * keep[i] / (1 - p): mask_dev {0,1} floats [n], or NULL = Philox keyed by (seed, stream_id).  Its
+ *                             adjoint is the same call on dy. */
+typedef struct ttsc_g2p_train_args {
+    const float* enc_dev;        /* [B, N, E] */
+    const float* pe_dev;         /* [B, N, A] = enc . W_att[:, D:]^T + b_att */
+    const int32_t* y_dev;        /* [B, T] teacher labels */
+    const float* w_aq;           /* W_att[:, :D] packed [D/4][A][4] */
+    const float* v;              /* [A] */
+    const float* w_ic;           /* W_ih0[:, :E] packed [E/4][4D][4] */
+    const float* tab;            /* [L, 4D] */
+    const float* w_hh0;          /* packed [D/4][4D][4] */
+    const float* b0;             /* [4D] b_ih + b_hh */
+    const float* w_ih1;          /* packed [D/4][4D][4] */
+    const float* w_hh1;          /* packed [D/4][4D][4] */
+    const float* b1;             /* [4D] */
+    const float* w_l1t;          /* [W_ih1^T; W_hh1^T] ([2D, 4D]) packed [4D/4][2D][4]   (backward) */
+    const float* w_l0t;          /* [W_hh0^T; W_ic^T] ([D + E, 4D]) packed [4D/4][D + E][4]   (backward) */
+    const float* w_aqt;          /* W_att[:, :D]^T ([D, A]) packed [A/4][D][4]   (backward) */
+    const float* att_mask_dev;   /* [B, T, N, A] {0,1} or NULL */
+    const float* dec_mask_dev;   /* [B, T + 1, D] {0,1} or NULL */
+    float* gates0_dev;           /* [B, T + 1, 4D] saved */
+    float* cells0_dev;           /* [B, T + 1, D] */
+    float* h1_dev;               /* [B, T + 1, D] */
+    float* h1m_dev;              /* [B, T + 1, D] h1 through the inter-layer dropout */
+    float* gates1_dev;           /* [B, T + 1, 4D] */
+    float* cells1_dev;           /* [B, T + 1, D] */
+    float* h2_dev;               /* [B, T + 1, D] */
+    float* aq_dev;               /* [B, T, A] */
+    float* att_dev;              /* [B, T, N] */
+    float* x0_dev;               /* [B, T + 1, E + Em]; the forward writes columns [0, E) of rows 1 .. T */
+    const float* dh2_dev;        /* [B, T, D]   (backward) */
+    float* dgates0_dev;          /* [B, T + 1, 4D]   (backward outputs) */
+    float* dgates1_dev;          /* [B, T + 1, 4D] */
+    float* dq_dev;               /* [B, T + 1, A] */
+    float* denc_dev;             /* [B, N, E] */
+    float* dpe_dev;              /* [B, N, A] */
+    float* dv_dev;               /* [B, A] */
+    float* scratch_dev;          /* [B, 2, N] */
+    uint64_t seed;
+    int32_t B, N, T, E, A, D, L, Em, stream_id;
+    float p_att, p_dec;
+} ttsc_g2p_train_args;
+int ttsc_g2p_train_forward(const ttsc_g2p_train_args* args, void* stream);
+int ttsc_g2p_train_backward(const ttsc_g2p_train_args* args, void* stream);
+int ttsc_dropout_scale(const float* x_dev, int64_t n, float p, const float* mask_dev, uint64_t seed, int32_t stream_id, float* y_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,16 @@ class G2pArgs(C.Structure):
                [(n, C.c_int32) for n in ('B', 'Nmax', 'T', 'E', 'A', 'D', 'L', 'eos', 'stop')]
 
 
+class G2pTrainArgs(C.Structure):
+    """ttsc_g2p_train_args (include/ttscube_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ('enc_dev', 'pe_dev', 'y_dev', 'w_aq', 'v', 'w_ic', 'tab', 'w_hh0', 'b0', 'w_ih1', 'w_hh1', 'b1', 'w_l1t',
+                                          'w_l0t', 'w_aqt', 'att_mask_dev', 'dec_mask_dev', 'gates0_dev', 'cells0_dev', 'h1_dev', 'h1m_dev',
+                                          'gates1_dev', 'cells1_dev', 'h2_dev', 'aq_dev', 'att_dev', 'x0_dev', 'dh2_dev', 'dgates0_dev',
+                                          'dgates1_dev', 'dq_dev', 'denc_dev', 'dpe_dev', 'dv_dev', 'scratch_dev')] + \
+               [('seed', C.c_uint64)] + [(n, C.c_int32) for n in ('B', 'N', 'T', 'E', 'A', 'D', 'L', 'Em', 'stream_id')] + \
+               [('p_att', C.c_float), ('p_dec', C.c_float)]
+
+
 WR_OUT_MULAW, WR_OUT_RAW, WR_OUT_MOL, WR_OUT_GM, WR_OUT_BETA = 0, 1, 2, 3, 4
 WR_MODE_ARGMAX, WR_MODE_NOISE, WR_MODE_PHILOX = 0, 1, 2
 
@@ -243,6 +253,9 @@ SIGNATURES = {
     'ttsc_g2p_decode': (C.c_int, [C.POINTER(G2pArgs), C.c_void_p]),
     'ttsc_g2p_embed': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'ttsc_g2p_status': (C.c_int32, []),
+    'ttsc_g2p_train_forward': (C.c_int, [C.POINTER(G2pTrainArgs), C.c_void_p]),
+    'ttsc_g2p_train_backward': (C.c_int, [C.POINTER(G2pTrainArgs), C.c_void_p]),
+    'ttsc_dropout_scale': (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 

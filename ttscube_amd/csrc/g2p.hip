@@ -275,6 +275,9 @@ inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 
 }  // namespace
 
+// the same word for the training kernels (g2p_train.hip): one ttsc_g2p_status covers both
+unsigned* g2p_status_word() { return status_word(); }
+
 }  // namespace ttsc
 
 using namespace ttsc;

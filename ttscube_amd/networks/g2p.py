@@ -1,5 +1,5 @@
 """Mirror of cube/networks/g2p.py: ``G2P`` — the word-level grapheme-to-phoneme front-end (attention seq2seq + pronunciation lexicon) behind
-``io_utils.io_text.Text2Feat`` — ``G2PDataset`` and the command line of the reference's file.  Inference only.
+``io_utils.io_text.Text2Feat`` — ``G2PDataset`` and the command line of the reference's file.  Inference; the training path is networks/g2p_train.py.
 
     words -> token ids (g2p.py:123-137: lower-cased characters, <UNK> = 1, <EOS> = 2 at position len, <PAD> = 0 after; N = longest word + 1)
           -> Seq2Seq.transcribe_ids (one ttsc_g2p_decode launch for all words, each stopping at its own first <EOS>)
@@ -12,7 +12,8 @@ utterances in one launch, every word padded to its own utterance's N.
 
     python -m ttscube_amd.networks.g2p --test-file FILE --load BASE                        word accuracy
     python -m ttscube_amd.networks.g2p --transcribe-file FILE --model BASE --output-file OUT
-Training (the reference's third mode) is not built: the command exits non-zero."""
+Training (the reference's third mode) is not built INTO THIS COMMAND, which exits non-zero there: it is scripts/train_g2p.py (same flags and files) on
+networks/g2p_train.py (learn_batch, g2p_training_step: the HIP attention-decoder forward / backward)."""
 import json
 import optparse
 import os
@@ -239,7 +240,8 @@ def main(argv):
         _transcribe(params)
     else:
         sys.stderr.write('G2P training is not built here (no attention / decoder backward); checkpoints trained by the reference load unchanged. '
-                         'Use --test-file FILE --load BASE or --transcribe-file FILE --model BASE --output-file OUT.\n')
+                         'Use --test-file FILE --load BASE or --transcribe-file FILE --model BASE --output-file OUT; to train, run scripts/train_g2p.py '
+                         '(networks/g2p_train.py).\n')
         return 2
     return 0
 

@@ -81,12 +81,45 @@ class HipLSTMLayerFn(torch.autograd.Function):
         return (dx, None) + tuple(grads)
 
 
-def lstm_forward_train(m, x):
-    """Differentiable forward of a torch.nn.LSTM parameter set `m` (batch_first, zero initial state) on the HIP kernels."""
+class HipDropoutFn(torch.autograd.Function):
+    """y = x * keep / (1 - p) (ttsc_dropout_scale): keep is an injected {0,1} mask of x's shape or drawn from Philox (seed, stream); the adjoint is
+    the same call on dy"""
+
+    @staticmethod
+    def _run(x, mask, p, seed, stream):
+        x = x.contiguous().float()
+        y = torch.empty_like(x)
+        with _lib.on_device(x.device):
+            _lib.check(_lib.lib().ttsc_dropout_scale(_lib.dev_ptr(x), x.numel(), float(p), _lib.dev_ptr(mask) if mask is not None else None, int(seed),
+                                                     int(stream), _lib.dev_ptr(y), _lib.current_stream()), 'ttsc_dropout_scale')
+        return y
+
+    @staticmethod
+    def forward(ctx, x, mask, p, seed, stream):
+        if mask is not None:
+            if tuple(mask.shape) != tuple(x.shape):
+                raise _lib.TTSCError('HipDropoutFn: the mask must have the shape of its input (%s, got %s)' % (tuple(x.shape), tuple(mask.shape)))
+            mask = mask.to(x.device).float().contiguous()
+        ctx.mask, ctx.args = mask, (float(p), int(seed), int(stream))
+        return HipDropoutFn._run(x, mask, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return HipDropoutFn._run(dy, ctx.mask, *ctx.args), None, None, None, None
+
+
+def lstm_forward_train(m, x, dropout_masks=None, dropout_seed=None):
+    """Differentiable forward of a torch.nn.LSTM parameter set `m` (batch_first, zero initial state) on the HIP kernels.
+    A module with dropout > 0 in training mode drops out between its layers as torch.nn.LSTM does (the whole output of every layer but the last,
+    one mask, scaled 1 / (1 - p)): dropout_masks = one {0,1} tensor [B, T, ndir * H] per layer but the last (parity tests), or dropout_seed = the
+    Philox seed (layer l draws stream l).  With dropout 0 neither is looked at."""
     if not x.is_cuda:
         raise _lib.TTSCError('LSTM training needs a HIP device; no CPU path')
     nd = 2 if m.bidirectional else 1
-    assert m.batch_first and float(m.dropout) == 0.0
+    assert m.batch_first
+    p = float(m.dropout) if m.training else 0.0
+    if p > 0.0 and m.num_layers > 1 and dropout_masks is None and dropout_seed is None:
+        raise _lib.TTSCError('lstm_forward_train: the module has dropout %g between its layers; pass dropout_masks or dropout_seed' % p)
     h = x
     for l in range(m.num_layers):
         ps = []
@@ -94,4 +127,6 @@ def lstm_forward_train(m, x):
             ps += [getattr(m, 'weight_ih_l%d%s' % (l, sfx)), getattr(m, 'weight_hh_l%d%s' % (l, sfx)),
                    getattr(m, 'bias_ih_l%d%s' % (l, sfx)), getattr(m, 'bias_hh_l%d%s' % (l, sfx))]
         h = HipLSTMLayerFn.apply(h, nd, *ps)
+        if p > 0.0 and l < m.num_layers - 1:
+            h = HipDropoutFn.apply(h, dropout_masks[l] if dropout_masks is not None else None, p, dropout_seed or 0, l)
     return h

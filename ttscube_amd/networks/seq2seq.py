@@ -194,7 +194,8 @@ class Seq2Seq(nn.Module):
 
     def _check_input(self, x, n=None):
         if self.training and torch.is_grad_enabled():
-            raise _lib.TTSCError('Seq2Seq: G2P training is not built (no attention / decoder backward); call eval() or run under torch.no_grad()')
+            raise _lib.TTSCError('Seq2Seq: G2P training is not built into forward() (no attention / decoder backward here); call eval() or run under '
+                                 'torch.no_grad(), or train through networks/g2p_train.py (scripts/train_g2p.py)')
         dev = self._get_device()
         if not x.is_cuda:
             raise _lib.TTSCError('Seq2Seq: token ids must live on a HIP device; no CPU path')
