@@ -217,6 +217,16 @@ int ttsc_rows_scatter_add(const float* gout_dev, const int32_t* idx_dev, float* 
                           void* stream);
 /* the same adjoint for a NON-DECREASING index list (phoneme rows -> frame rows, cube/networks/modules.py:1043-1053): O(n C) instead of O(V n C) */
 int ttsc_rows_segment_sum(const float* gout_dev, const int32_t* idx_sorted_dev, float* gtable_dev, int64_t n, int32_t C, int32_t V, void* stream);
+/* Phoneme rows of the word-conditioned text stacks (cube/networks/modules.py:930-940, 976-988, 1079-1082), one launch each way:
+ *   out [B, N, Ch + Cs + Cw] = [ h[b, n, :] | spk[b, :] | cond[b, p2w[b, n], :] ]          h [B, N, Ch], spk [B, Cs], cond [B, Nw, Cw], p2w [B, N]
+ *   gh = gout[:, :, :Ch],  gspk[b] = sum_n gout[b, n, Ch:Ch + Cs],  gcond[b, w] = sum_{n: p2w[b, n] == w} gout[b, n, Ch + Cs:]
+ * The forward is a copy (bit-equal to cat / repeat / index); the sums run over n ascending inside one thread, without atomics (the same bits on
+ * every run), a word no phoneme points at gets zeros, p2w need not be monotone.  p2w must lie in [0, Nw): the CALLER checks its host copy — the
+ * kernels read an index outside that range as a zero row / skip it, they never touch memory through it. */
+int ttsc_phone_rows_assemble(const float* h_dev, const float* spk_dev, const float* cond_dev, const int32_t* p2w_dev, float* out_dev, int32_t B, int32_t N,
+                             int32_t Nw, int32_t Ch, int32_t Cs, int32_t Cw, void* stream);
+int ttsc_phone_rows_assemble_bwd(const float* gout_dev, const int32_t* p2w_dev, float* gh_dev, float* gspk_dev, float* gcond_dev, int32_t B, int32_t N,
+                                 int32_t Nw, int32_t Ch, int32_t Cs, int32_t Cw, void* stream);
 /* Polyphase de-interleave of a strided Conv1d's operands (the discriminators' stride-2/3/4 layers [EXTERNAL hifigan/models.py DiscriminatorP /
  * DiscriminatorS; call sites cube/networks/cubegan.py:144-149,160-167]): the layer runs as a stride-1 convolution over
  *   xr[n, (g, r, ci), m P + w] = x[n, (g, ci), ((m s + r) - pad) P + w]   (zero outside; P = 1 or MPD's period, rows of P samples)

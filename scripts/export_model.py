@@ -4,6 +4,8 @@
 
   <in>.last / .yaml / .encodings  ->  <in>.model            inference weights: the discriminators and the dummy parameter dropped
                                       <out>-00, <out>-01 …  a gzip tar of cubegan.{model,yaml,encodings} [+ phonemizer.{model,encodings}]
+                                                            [+ cubegan.vec / cubegan.vectors.npz: the word-vector table of a `fasttext:<lang>`
+                                                            model, when one sits next to the checkpoint]
                                                             cut into volumes of at most 49 MiB (the hosting limit the reference's format works around)
                                       <out>.yaml            {version, phonemizer: sentence, synthesis: cubegan, language, description}
 """
@@ -37,6 +39,7 @@ def strip_to_inference_weights(base):
 
 def archive_members(base, phonemizer):
     members = [(base + '.' + ext, 'cubegan.' + ext) for ext in ('model', 'yaml', 'encodings')]
+    members += [(base + '.' + ext, 'cubegan.' + ext) for ext in ('vec', 'vectors.npz') if os.path.exists(base + '.' + ext)]
     if phonemizer:
         members += [(phonemizer + '.sacc.best', 'phonemizer.model'), (phonemizer + '.encodings', 'phonemizer.encodings')]
     return members

@@ -14,7 +14,13 @@ like DistributedSampler, so all ranks run the same number of steps and gradient 
 background threads one batch ahead of the GPU step; the dev set is validated in rank shards and the loss sums are all-reduced.  `.best` is selected on the
 DEV-set mel-L1 (Cubegan.validation_step / validation_epoch_end, cubegan.py:191-273), as the reference does.  With
 `--synthetic N` the folders are ignored and N seeded synthetic examples per rank (+ N/4 for the dev set) are used instead —
-that must be asked for explicitly: a missing or empty folder is an error, never a silent fall-back."""
+that must be asked for explicitly: a missing or empty folder is an error, never a silent fall-back.
+
+`--lm fasttext:<lang> --word-vectors <file>` trains the word-conditioned model (the configuration the reference's own trainer produces): the
+collate reads every word's vector from the local table (.vec text format or .npz, io_utils/word_vectors.py; a word it does not hold gives zeros),
+the yaml records `conditioning: fasttext:<lang>` and the vectors of the words the train and dev sets use are written to
+<base>.vectors.npz, where `TTSCube` and scripts/export_model.py look for them (a word outside the corpus gives zeros at run time unless the
+full table is passed as `word_vectors=`).  With `--synthetic` and no file, seeded random vectors over the synthetic vocabulary are used."""
 import os
 import random
 import sys
@@ -47,11 +53,26 @@ def _train(params):
     if world > 1:
         dist.init_process_group('nccl', device_id=dev)
     conditioning = params.lm if params.lm not in (None, 'none') else None
+    table, nwords = None, None
+    if conditioning is not None:
+        if not conditioning.startswith('fasttext'):
+            raise SystemExit('--lm %s: only none and fasttext:<lang> (with --word-vectors) are built; the HuggingFace encoders cannot be downloaded here' % conditioning)
+        from ttscube_amd.io_utils.word_vectors import WordVectors
+        if params.word_vectors:
+            table = WordVectors(params.word_vectors)
+        elif params.synthetic:
+            from ttscube_amd.io_utils.synthetic import SYNTHETIC_VOCABULARY
+            table = WordVectors.synthetic(SYNTHETIC_VOCABULARY, dim=300, seed=2024)      # identical on every rank
+        else:
+            raise SystemExit('--lm %s needs --word-vectors <file> (.vec text format or .npz with words / vectors)' % conditioning)
+        if table.dim != 300:
+            raise SystemExit('--word-vectors: fasttext conditioning takes 300-d vectors (cube/networks/modules.py:823), the table has %d' % table.dim)
     if params.synthetic:
-        trainset = list(synthetic_examples(params.synthetic, 1234 + rank))          # rank-distinct data and crops, same count on every rank
-        devset = list(synthetic_examples(max(2, params.synthetic // 4), 4321))
+        nwords = 6 if table is not None else None      # conditioned synthetic sentences: words, a left context and sometimes a right one
+        trainset = list(synthetic_examples(params.synthetic, 1234 + rank, words=nwords))   # rank-distinct data and crops, same count on every rank
+        devset = list(synthetic_examples(max(2, params.synthetic // 4), 4321, words=nwords))
         my_items = list(range(len(trainset)))
-        enc_source = list(synthetic_examples(params.synthetic, 1234)) if world > 1 else trainset
+        enc_source = list(synthetic_examples(params.synthetic, 1234, words=nwords)) if world > 1 else trainset
     else:
         from ttscube_amd.io_utils.io_cubegan import CubeganDataset
         for folder in (params.train_folder, params.dev_folder):
@@ -72,6 +93,15 @@ def _train(params):
         yaml.dump({'sample_rate': params.sample_rate, 'hop_size': params.hop_size, 'conditioning': conditioning},
                   open('{0}.yaml'.format(params.output_base), 'w'))
         enc.save('{0}.encodings'.format(params.output_base))
+        if table is not None:
+            # the vectors travel with the checkpoint (api.TTSCube and scripts/export_model.py look for them beside the model) — only those of the
+            # words the corpus uses: a distributed table holds millions of words and several GB, a corpus a few thousand
+            if params.synthetic:
+                from ttscube_amd.io_utils.synthetic import SYNTHETIC_VOCABULARY as vocabulary      # (every rank's examples draw from it)
+            else:
+                vocabulary = [w for ds in (trainset, devset) for ex in ds._examples
+                              for w in list(ex.get('words_left', [])) + list(ex.get('words', [])) + list(ex.get('words_right', []))]
+            table.subset(vocabulary).save_npz('{0}.vectors.npz'.format(params.output_base))
     model = Cubegan(enc, lr=params.lr, conditioning=conditioning, train=True)
     if params.resume:
         model.load('{0}.last'.format(params.output_base))
@@ -82,7 +112,7 @@ def _train(params):
     broadcast_parameters(model)
     opts = T.cubegan_configure_optimizers(model)
     reducers = T.cubegan_reducers(model, opts) if world > 1 else None   # reduce_scatters leave from bucket-ready gradient hooks
-    collate = CubeganCollate(enc)
+    collate = CubeganCollate(enc, conditioning_type=conditioning, word_vectors=table)
     crop_rng = random.Random(99 + rank)
     best = 9999.0
     val_rng = random.Random(7)
@@ -126,7 +156,7 @@ def _train(params):
                 model.eval()
                 # bounded: the other ranks wait in the barrier below while rank 0 synthesises (default 16 files, not the whole dev set)
                 cubegan_synthesize_dataset(model, output_path='generated_files/free/', devset_path=params.dev_folder,
-                                           limit=params.generate_limit, conditioning=conditioning)
+                                           limit=params.generate_limit, conditioning=conditioning, word_vectors=table)
                 model.train()
         if world > 1:
             dist.barrier()
@@ -147,7 +177,9 @@ if __name__ == '__main__':
     p.add_argument('--sample-rate', dest='sample_rate', type=int, default=24000)
     p.add_argument('--hop-size', dest='hop_size', type=int, default=240)
     p.add_argument('--lr', dest='lr', default=2e-4, type=float)
-    p.add_argument('--lm', dest='lm', default=None, help='external conditioning (none | fasttext:<lang> | hf:<model>); only none is built')
+    p.add_argument('--lm', dest='lm', default=None, help='external conditioning: none | fasttext:<lang> (word vectors from --word-vectors; hf:<model> is not built)')
+    p.add_argument('--word-vectors', dest='word_vectors', default=None,
+                   help='local word-vector table for --lm fasttext:<lang>: fastText .vec text format, or .npz with words / vectors')
     p.add_argument('--resume', dest='resume', action='store_true')
     p.add_argument('--epochs', type=int, default=1)
     p.add_argument('--miopen-find', dest='miopen_find', action='store_true', help='let MIOpen search its convolution algorithms exhaustively (see _train)')

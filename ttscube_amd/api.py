@@ -7,7 +7,11 @@ The text front-end: when ``<phonemizer_path>.encodings`` and ``<phonemizer_path>
 callable ``text -> {'phones': [...], 'words': [...], 'phon2word': [...]}`` overrides it (the reference's Text2Feat* objects
 satisfy it); with neither, the text is read as whitespace-separated phoneme symbols.
 New on top of the reference (B=1 only): ``synthesize_batch`` runs many sentences per call, length-bucketed, and
-``shard`` splits a sentence list across ranks (one process per GPU, no collectives)."""
+``shard`` splits a sentence list across ranks (one process per GPU, no collectives).
+
+A model trained with ``conditioning: fasttext:<lang>`` (the yaml's key) needs the word-vector table it was trained with: ``word_vectors=`` takes a path
+(.vec / .npz) or a ``WordVectors``; by default ``<model_path>.vectors.npz`` (what the trainer writes: the corpus vocabulary) or ``<model_path>.vec`` is read when present.  The front end's ``words`` are
+looked up there; at run time a sentence has no left or right context, so ``x_phon2word`` is the front end's ``phon2word`` itself."""
 import os
 from pathlib import Path
 
@@ -34,13 +38,27 @@ class PhoneText2Feat:
 
 
 class TTSCube:
-    def __init__(self, model_path: str, phonemizer_path: str = None, text2feat=None, device='cuda:0'):
+    def __init__(self, model_path: str, phonemizer_path: str = None, text2feat=None, device='cuda:0', word_vectors=None):
         encodings = CubeganEncodings('{0}.encodings'.format(model_path))
         conf = yaml.load(open('{0}.yaml'.format(model_path)), yaml.Loader)
         cond_type = conf.get('conditioning')
+        if cond_type in (None, 'none'):
+            cond_type = None
+        table = None
+        if cond_type is not None and str(cond_type).startswith('fasttext'):
+            from .io_utils.word_vectors import WordVectors
+            if word_vectors is None:
+                word_vectors = next((p for p in ('{0}.vectors.npz'.format(model_path), '{0}.vec'.format(model_path)) if os.path.exists(p)), None)
+            if word_vectors is None:
+                raise _lib.TTSCError("%s.yaml says conditioning: %s, but no word-vector table was given and neither %s.vec nor %s.vectors.npz exists; "
+                                     "pass word_vectors= (a path or a WordVectors): the model cannot run without the vectors it was trained with"
+                                     % (model_path, cond_type, model_path, model_path))
+            table = WordVectors.resolve(word_vectors)
+            if table.dim != 300:
+                raise _lib.TTSCError('word_vectors: fasttext conditioning takes 300-d vectors, the table has %d' % table.dim)
         self._model = Cubegan(encodings, conditioning=cond_type, train=False)
         self._model.load('{0}.model'.format(model_path))
-        self._collate = CubeganCollate(encodings, conditioning_type=cond_type)
+        self._collate = CubeganCollate(encodings, conditioning_type=cond_type, word_vectors=table)
         self._model.eval()
         self._model.to(device)
         self._text2feat = self._make_text2feat(phonemizer_path, text2feat, device)
@@ -88,7 +106,7 @@ class TTSCube:
         if not os.path.exists('{0}/cubegan.model'.format(base_name)):
             raise FileNotFoundError('%s/cubegan.{model,yaml,encodings} not found and this build has no network access to '
                                     'download it (cube/io_utils/repository.py:27-61); unpack the exported model there' % base_name)
-        return TTSCube('{0}/cubegan'.format(base_name), '{0}/phonemizer'.format(base_name), **kw)
+        return TTSCube('{0}/cubegan'.format(base_name), '{0}/phonemizer'.format(base_name), **kw)      # (**kw: text2feat, device, word_vectors)
 
     def _example(self, text, speaker, feats=None):
         """The dummy-target example cube/api.py:47-57 builds around the front-end output (`feats`: that output, when the caller already has it)."""
@@ -128,7 +146,8 @@ class TTSCube:
     def synthesize_batch(self, texts, speaker='none', max_batch=64):
         """Many sentences -> list of int16 arrays (same order).  Sentences are sorted by phoneme count and run in
         padded batches of up to `max_batch`; ragged lengths are handled inside the kernels (masked BiLSTMs), so each
-        result equals the single-sentence call."""
+        result equals the single-sentence call — with word conditioning too: the collate's word counts (x_words_len) stop the word BiLSTMs at each
+        sentence's own last word."""
         speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
         # a front-end with a `batch` method (io_text.Text2FeatBlizzard) phonemizes the whole list in one padded call
         feats = self._text2feat.batch(list(texts)) if hasattr(self._text2feat, 'batch') else [None] * len(texts)

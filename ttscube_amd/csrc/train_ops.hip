@@ -248,6 +248,79 @@ __global__ __launch_bounds__(256) void rows_scatter_add_kernel(const float* __re
     }
 }
 
+// ---- phoneme rows with word conditioning (cube/networks/modules.py:930-940, 976-988, 1079-1082) ---------------------------------------------
+// out[b, n, :] = [ h[b, n, :Ch] | spk[b, :Cs] | cond[b, p2w[b, n], :Cw] ]: the input row of `_dur_rnn` / `_expand_i` when a word encoder conditions
+// the text stacks.  A pure copy: every thread moves one ELEMENT of V (float4 when the three widths are multiples of 4 — 16-byte accesses, lanes on
+// consecutive columns of a row; float otherwise).  An index outside [0, Nw) reads as a zero row (the callers reject such a list before they launch).
+template <typename V>
+__global__ __launch_bounds__(256) void phone_rows_assemble_kernel(const V* __restrict__ h, const V* __restrict__ spk, const V* __restrict__ cond,
+                                                                  const int* __restrict__ p2w, V* __restrict__ out, long rows, int N, int Nw, int Qh, int Qs,
+                                                                  int Qw) {
+    const int Qt = Qh + Qs + Qw;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < rows * Qt; e += (long)gridDim.x * 256) {
+        const long r = e / Qt;                 // (b, n)
+        const int q = (int)(e - r * Qt);
+        const long b = r / N;
+        V v;
+        if (q < Qh) {
+            v = h[r * Qh + q];
+        } else if (q < Qh + Qs) {
+            v = spk[b * Qs + (q - Qh)];
+        } else {
+            const int w = p2w[r];
+            v = (w >= 0 && w < Nw) ? cond[(b * Nw + w) * Qw + (q - Qh - Qs)] : V{};
+        }
+        out[e] = v;
+    }
+}
+
+__device__ inline void phone_rows_add(float& a, const float& b) { a += b; }
+__device__ inline void phone_rows_add(float4& a, const float4& b) {
+    a.x += b.x;
+    a.y += b.y;
+    a.z += b.z;
+    a.w += b.w;
+}
+
+// The adjoint, three gradients in one launch over one flat list of work items (one element of V each):
+//   [0, rows Qh)             gh[b, n, q]    = gout[b, n, q]                                                 a strided copy
+//   then B Qs items          gspk[b, q]     = sum_n gout[b, n, Ch + q]                                      n ascending
+//   then B Nw Qw items       gcond[b, w, q] = sum_{n : p2w[b, n] == w} gout[b, n, Ch + Cs + q]              n ascending; no n -> zeros
+// Every sum lives in ONE thread that walks the utterance's phonemes in order — no atomics, the same bits on every run — and the lanes of a wave
+// hold consecutive columns, so each step of the walk reads whole lines of gout and one broadcast index.  p2w need not be monotone (padding rows carry 0,
+// and count for word 0 as they do in the reference).
+template <typename V>
+__global__ __launch_bounds__(256) void phone_rows_assemble_bwd_kernel(const V* __restrict__ gout, const int* __restrict__ p2w, V* __restrict__ gh,
+                                                                      V* __restrict__ gspk, V* __restrict__ gcond, int B, int N, int Nw, int Qh, int Qs,
+                                                                      int Qw) {
+    const int Qt = Qh + Qs + Qw;
+    const long nh = (long)B * N * Qh, ns = (long)B * Qs, nc = (long)B * Nw * Qw;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nh + ns + nc; e += (long)gridDim.x * 256) {
+        if (e < nh) {
+            const long r = e / Qh;
+            gh[e] = gout[r * Qt + (e - r * Qh)];
+        } else if (e < nh + ns) {
+            const long i = e - nh;
+            const long b = i / Qs;
+            const V* src = gout + b * N * Qt + Qh + (i - b * Qs);
+            V acc{};
+            for (int n = 0; n < N; ++n) phone_rows_add(acc, src[(long)n * Qt]);
+            gspk[i] = acc;
+        } else {
+            const long i = e - nh - ns;
+            const long bw = i / Qw;            // (b, w)
+            const long b = bw / Nw;
+            const int w = (int)(bw - b * Nw);
+            const V* src = gout + b * N * Qt + Qh + Qs + (i - bw * Qw);
+            const int* pw = p2w + b * N;
+            V acc{};
+            for (int n = 0; n < N; ++n)
+                if (pw[n] == w) phone_rows_add(acc, src[(long)n * Qt]);
+            gcond[i] = acc;
+        }
+    }
+}
+
 
 // ---- polyphase de-interleave of a strided convolution's operands (hifigan/disc_hip.py::HipStridedConv) ------------------------------------
 // A Conv1d with stride s runs as a stride-1 convolution over  xr[n, (g, r, ci), m P + w] = x[n, (g, ci), ((m s + r) - pad) P + w]  (zero outside the
@@ -662,6 +735,47 @@ extern "C" int ttsc_rows_scatter_add(const float* gout_dev, const int32_t* idx_d
     TTSC_REQUIRE(gout_dev && idx_dev && gtable_dev && n > 0 && C > 0 && V > 0, "ttsc_rows_scatter_add: bad argument");
     hipLaunchKernelGGL(rows_scatter_add_kernel, dim3((unsigned)V), dim3(256), 0, (hipStream_t)stream, gout_dev, idx_dev, gtable_dev, (long)n, C, skip_row);
     return check_launch("rows_scatter_add_kernel");
+}
+
+static bool phone_rows_vec4(int32_t Ch, int32_t Cs, int32_t Cw, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = (uintptr_t)(Ch | Cs | Cw) & 3;
+    for (const void* p : ptrs) bits |= (uintptr_t)p & 15;
+    return bits == 0;
+}
+
+extern "C" int ttsc_phone_rows_assemble(const float* h_dev, const float* spk_dev, const float* cond_dev, const int32_t* p2w_dev, float* out_dev, int32_t B,
+                                        int32_t N, int32_t Nw, int32_t Ch, int32_t Cs, int32_t Cw, void* stream) {
+    TTSC_REQUIRE(h_dev && spk_dev && cond_dev && p2w_dev && out_dev, "ttsc_phone_rows_assemble: null argument");
+    TTSC_REQUIRE(B > 0 && N > 0 && Nw > 0 && Ch > 0 && Cs > 0 && Cw > 0, "ttsc_phone_rows_assemble: bad sizes");
+    const long rows = (long)B * N;
+    if (phone_rows_vec4(Ch, Cs, Cw, {h_dev, spk_dev, cond_dev, out_dev})) {
+        const long total = rows * ((Ch + Cs + Cw) / 4);
+        hipLaunchKernelGGL(phone_rows_assemble_kernel<float4>, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                           (const float4*)h_dev, (const float4*)spk_dev, (const float4*)cond_dev, p2w_dev, (float4*)out_dev, rows, N, Nw, Ch / 4, Cs / 4,
+                           Cw / 4);
+    } else {
+        const long total = rows * ((long)Ch + Cs + Cw);
+        hipLaunchKernelGGL(phone_rows_assemble_kernel<float>, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                           h_dev, spk_dev, cond_dev, p2w_dev, out_dev, rows, N, Nw, Ch, Cs, Cw);
+    }
+    return check_launch("phone_rows_assemble_kernel");
+}
+
+extern "C" int ttsc_phone_rows_assemble_bwd(const float* gout_dev, const int32_t* p2w_dev, float* gh_dev, float* gspk_dev, float* gcond_dev, int32_t B,
+                                            int32_t N, int32_t Nw, int32_t Ch, int32_t Cs, int32_t Cw, void* stream) {
+    TTSC_REQUIRE(gout_dev && p2w_dev && gh_dev && gspk_dev && gcond_dev, "ttsc_phone_rows_assemble_bwd: null argument");
+    TTSC_REQUIRE(B > 0 && N > 0 && Nw > 0 && Ch > 0 && Cs > 0 && Cw > 0, "ttsc_phone_rows_assemble_bwd: bad sizes");
+    if (phone_rows_vec4(Ch, Cs, Cw, {gout_dev, gh_dev, gspk_dev, gcond_dev})) {
+        const long total = (long)B * N * (Ch / 4) + (long)B * (Cs / 4) + (long)B * Nw * (Cw / 4);
+        hipLaunchKernelGGL(phone_rows_assemble_bwd_kernel<float4>, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0,
+                           (hipStream_t)stream, (const float4*)gout_dev, p2w_dev, (float4*)gh_dev, (float4*)gspk_dev, (float4*)gcond_dev, B, N, Nw, Ch / 4,
+                           Cs / 4, Cw / 4);
+    } else {
+        const long total = (long)B * N * Ch + (long)B * Cs + (long)B * Nw * Cw;
+        hipLaunchKernelGGL(phone_rows_assemble_bwd_kernel<float>, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0,
+                           (hipStream_t)stream, gout_dev, p2w_dev, gh_dev, gspk_dev, gcond_dev, B, N, Nw, Ch, Cs, Cw);
+    }
+    return check_launch("phone_rows_assemble_bwd_kernel");
 }
 
 

@@ -1,7 +1,8 @@
 """Mirror of cube/io_utils/io_cubegan.py: ``CubeganDataset`` (:20-110, the processed-corpus reader: <id>.json / .mgc / .pitch /
 .wav), ``CubeganEncodings`` (:112-160, same JSON file format) and ``CubeganCollate.collate_fn`` (:162-231, same batch-dict keys,
-dtypes and padding values — SURVEY.md §8b).  External text conditioning (fastText / HF encoders) needs downloads and is not
-available here — pass pre-computed ``x_words`` instead."""
+dtypes and padding values — SURVEY.md §8b).  `fasttext:<lang>` conditioning reads its word vectors from a local table
+(``word_vectors=``: io_utils/word_vectors.py) instead of downloading a fastText model; the HF encoders are not available here — pass
+pre-computed ``x_words`` instead."""
 import json
 import os
 
@@ -110,14 +111,31 @@ class CubeganEncodings:
 
 
 class CubeganCollate:
-    def __init__(self, encodings: CubeganEncodings, conditioning_type=None, training=True):
+    def __init__(self, encodings: CubeganEncodings, conditioning_type=None, training=True, word_vectors=None):
         self._encodings = encodings
         self._ignore_index = int(max(encodings.max_pitch, encodings.max_duration) + 1)
         self._training = training
-        if conditioning_type not in (None, 'none'):
-            raise NotImplementedError("conditioning_type=%r needs a downloaded fastText / HuggingFace model; this build "
-                                      "supports conditioning=None (SURVEY.md §2.1)" % (conditioning_type,))
         self._conditioning_type = None
+        self._ft = None
+        if conditioning_type not in (None, 'none') and str(conditioning_type).startswith('fasttext'):
+            if word_vectors is None:
+                raise NotImplementedError("conditioning_type=%r: the fastText model cannot be downloaded here; pass the word vectors you have as "
+                                          "word_vectors= (a WordVectors, or the path of a .vec / .npz table: io_utils/word_vectors.py)" % (conditioning_type,))
+            from .word_vectors import WordVectors
+            self._ft = WordVectors.resolve(word_vectors)      # (io_cubegan.py:161-165: `self._ft`, asked through get_word_vector)
+            self._conditioning_type = 'fasttext'
+        elif conditioning_type not in (None, 'none'):
+            raise NotImplementedError("conditioning_type=%r needs a downloaded HuggingFace model; this build supports conditioning=None and "
+                                      "'fasttext:<lang>' with word_vectors= (SURVEY.md §2.1)" % (conditioning_type,))
+
+    def _get_ft_embeddings(self, batch):
+        """io_cubegan.py:233-244: one row per word of left context ‖ sentence ‖ right context, zero rows behind the shorter examples"""
+        rows = [list(e['meta'].get('words_left', [])) + list(e['meta']['words']) + list(e['meta'].get('words_right', [])) for e in batch]
+        x_words = np.zeros((len(batch), max(max(len(r) for r in rows), 1), self._ft.dim), dtype=np.float32)
+        for ii, words in enumerate(rows):
+            for jj, w in enumerate(words):
+                x_words[ii, jj, :] = self._ft.get_word_vector(str(w))
+        return x_words
 
     def collate_fn(self, batch):
         """io_cubegan.py:169-231."""
@@ -141,6 +159,8 @@ class CubeganCollate:
             y_frame2phone.append(example['meta']['frame2phon'])
             p2w = example['meta'].get('phon2word', [])
             x_p2w[ii, :len(p2w)] = np.array(p2w, dtype=np.int64)
+            if self._conditioning_type == 'fasttext':           # (io_cubegan.py:198-199: the sentence's words sit behind its left context)
+                x_p2w[ii, :len(p2w)] += len(example['meta'].get('words_left', []))
             for phone_idx in y_frame2phone[-1]:
                 y_dur[ii, phone_idx] += 1
             y_dur[ii, len(example['meta']['phones']):] = self._ignore_index
@@ -154,8 +174,15 @@ class CubeganCollate:
         # x_len is an addition to the reference's dict: the true phone count per example.  An out-of-vocabulary phone is encoded
         # as 0 — the padding id — so lengths cannot be recovered from x_char alone (batched inference masks by length).
         x_len = [len(e['meta']['phones']) for e in batch]
-        return {'x_char': torch.tensor(x_char, dtype=torch.long), 'x_len': torch.tensor(x_len, dtype=torch.long), 'x_words': None, 'x_tok_ids': None, 'x_word2tok': None,
+        x_words = torch.from_numpy(self._get_ft_embeddings(batch)) if self._conditioning_type == 'fasttext' else None
+        extra = {}
+        if x_words is not None:
+            # (an addition like x_len, present with word conditioning only: words per example, left and right context included — batched inference
+            # stops the word BiLSTMs there; training runs over the padding as the reference does)
+            extra['x_words_len'] = torch.tensor([len(e['meta'].get('words_left', [])) + len(e['meta']['words']) + len(e['meta'].get('words_right', []))
+                                                 for e in batch], dtype=torch.long)
+        return {'x_char': torch.tensor(x_char, dtype=torch.long), 'x_len': torch.tensor(x_len, dtype=torch.long), 'x_words': x_words, 'x_tok_ids': None, 'x_word2tok': None,
                 'x_phon2word': torch.tensor(x_p2w), 'x_speaker': torch.tensor(x_speaker, dtype=torch.long),
                 'y_mgc': torch.tensor(y_mgc, dtype=torch.float), 'y_frame2phone': y_frame2phone,
                 'y_pitch': torch.tensor(y_pitch, dtype=torch.long), 'y_dur': torch.tensor(y_dur, dtype=torch.long),
-                'y_audio': torch.tensor(y_audio, dtype=torch.float)}
+                'y_audio': torch.tensor(y_audio, dtype=torch.float), **extra}

@@ -13,8 +13,8 @@ from .audio import save_wav
 from .io_cubegan import CubeganCollate, CubeganDataset
 
 
-def cubegan_synthesize_dataset(model, output_path, devset_path, limit=-1, free=True, conditioning=None, speaker=None):
-    collate = CubeganCollate(model._encodings, conditioning_type=conditioning)
+def cubegan_synthesize_dataset(model, output_path, devset_path, limit=-1, free=True, conditioning=None, speaker=None, word_vectors=None):
+    collate = CubeganCollate(model._encodings, conditioning_type=conditioning, word_vectors=word_vectors)
     dataset = CubeganDataset(devset_path)
     m_gen = len(dataset) if limit == -1 or limit >= len(dataset) else limit
     os.makedirs(output_path, exist_ok=True)

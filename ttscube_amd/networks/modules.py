@@ -501,7 +501,11 @@ class Languasito2(nn.Module):
             if X.get('x_tok_ids') is not None:
                 raise NotImplementedError('conditioning=hf:<model>: supply X["x_words"] ([B,Nw,768] encoder states per word); '
                                           'pretrained encoders cannot be downloaded here (SURVEY.md §2.1)')
-            cond = self._lstm('_lm_' + which)(x_words.to(h.device).float())
+            # a padded batch: the word BiLSTM stops at each utterance's own word count (the collate's x_words_len), so that its reverse direction
+            # does not start inside the zero rows behind a shorter sentence — a sentence then gives the same states alone or in a batch
+            nw = X.get('x_words_len') if x_words.shape[0] > 1 else None
+            cond = self._lstm('_lm_' + which)(x_words.to(h.device).float(),
+                                              lengths=[int(v) for v in torch.as_tensor(nw).reshape(-1).tolist()] if nw is not None else None)
             p2w = X['x_phon2word'].to(h.device)
             sel = torch.gather(cond, 1, p2w[:, :, None].expand(-1, -1, cond.shape[2]))
             h = torch.cat([h, sel], dim=-1)

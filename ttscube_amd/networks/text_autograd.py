@@ -75,6 +75,62 @@ def hip_embedding(emb, idx):
     return HipEmbeddingFn.apply(emb.weight, idx, emb.padding_idx)
 
 
+def checked_phon2word(p2w, Nw, what='phone_rows_assemble'):
+    """phoneme -> word map [B, N] as the int32 host tensor the launches upload, after the range check the kernels rely on: an index outside [0, Nw)
+    raises here, before anything is launched (the collate hands the map over on the host; a device tensor is read back for the check)"""
+    host = p2w.detach().to('cpu', torch.int64)
+    if host.dim() != 2 or host.numel() == 0:
+        raise _lib.TTSCError('%s: x_phon2word must be a non-empty [B, N] tensor (got %s)' % (what, tuple(host.shape)))
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi >= Nw:
+        raise _lib.TTSCError('%s: x_phon2word holds word indices in [%d, %d] but x_words has %d rows per utterance' % (what, lo, hi, Nw))
+    return host.to(torch.int32).contiguous()
+
+
+class PhoneRowsAssembleFn(torch.autograd.Function):
+    """[h | speaker | cond[p2w]] per phoneme row (modules.py:930-940, 976-988, 1079-1082): h [B, N, Ch], spk [B, Cs], cond [B, Nw, Cw], p2w_dev int32
+    [B, N] on the device, range-checked by `checked_phon2word` -> [B, N, Ch + Cs + Cw].  One launch forward (a copy), one backward (the three
+    gradients; fixed-order sums: ttsc_phone_rows_assemble_bwd)"""
+
+    @staticmethod
+    def forward(ctx, h, spk, cond, p2w_dev):
+        h, spk, cond = h.contiguous().float(), spk.contiguous().float(), cond.contiguous().float()
+        B, N, Ch = h.shape
+        Nw, Cw = cond.shape[1], cond.shape[2]
+        Cs = spk.shape[-1]
+        if spk.numel() != B * Cs or cond.shape[0] != B or tuple(p2w_dev.shape) != (B, N) or p2w_dev.dtype != torch.int32 or not p2w_dev.is_contiguous():
+            raise _lib.TTSCError('PhoneRowsAssembleFn: h %s, spk %s, cond %s, p2w %s %s do not fit together' %
+                                 (tuple(h.shape), tuple(spk.shape), tuple(cond.shape), tuple(p2w_dev.shape), p2w_dev.dtype))
+        out = torch.empty((B, N, Ch + Cs + Cw), dtype=torch.float32, device=h.device)
+        with _lib.on_device(h.device):
+            _lib.check(_lib.lib().ttsc_phone_rows_assemble(_lib.dev_ptr(h), _lib.dev_ptr(spk), _lib.dev_ptr(cond), _lib.dev_ptr(p2w_dev), _lib.dev_ptr(out),
+                                                           B, N, Nw, Ch, Cs, Cw, _lib.current_stream()), 'ttsc_phone_rows_assemble')
+        ctx.save_for_backward(p2w_dev)
+        ctx.dims, ctx.spk_shape = (B, N, Nw, Ch, Cs, Cw), spk.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        p2w_dev, = ctx.saved_tensors
+        B, N, Nw, Ch, Cs, Cw = ctx.dims
+        g = g.contiguous()
+        gh = torch.empty((B, N, Ch), dtype=torch.float32, device=g.device)
+        gspk = torch.empty(ctx.spk_shape, dtype=torch.float32, device=g.device)
+        gcond = torch.empty((B, Nw, Cw), dtype=torch.float32, device=g.device)
+        with _lib.on_device(g.device):
+            _lib.check(_lib.lib().ttsc_phone_rows_assemble_bwd(_lib.dev_ptr(g), _lib.dev_ptr(p2w_dev), _lib.dev_ptr(gh), _lib.dev_ptr(gspk),
+                                                               _lib.dev_ptr(gcond), B, N, Nw, Ch, Cs, Cw, _lib.current_stream()),
+                       'ttsc_phone_rows_assemble_bwd')
+        return gh, gspk, gcond, None
+
+
+def phone_rows_assemble(h, spk, cond, p2w):
+    """the checked entry: `p2w` any integer tensor [B, N] (host or device)"""
+    if not h.is_cuda:
+        raise _lib.TTSCError('phone_rows_assemble: tensors must live on a HIP device (no CPU path)')
+    return PhoneRowsAssembleFn.apply(h, spk, cond, checked_phon2word(p2w, cond.shape[1]).to(h.device))
+
+
 def char_cnn_train(lang, name, h):
     """h [B, C, N] through the (ConvNorm k=3 pad=1, Tanh) x 3 stack `name` of `lang`; one TrainConv (forward / dgrad / wgrad handles) per layer"""
     cache = lang.__dict__.setdefault('_train_cnn', {})

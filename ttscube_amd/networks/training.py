@@ -36,6 +36,8 @@ def languasito_forward(lang, X):
     B = x_char.shape[0]
     lengths = _char_lengths(X, x_char) if B > 1 else None
     f2p = X['y_frame2phone']
+    if X.get('x_words_len') is not None:
+        X = {k: v for k, v in X.items() if k != 'x_words_len'}     # teacher-forced like the training step: the word BiLSTMs run over the padding rows too
     with torch.no_grad():
         hcs = lang._text_stack('t', x_char, x_speaker, lengths, X, None)
         hd = lang._lstm('_dur_rnn')(hcs, lengths=lengths)
@@ -177,20 +179,35 @@ def _languasito_branches(lang, X):
          text()  -> (output_dur, output_pitch, output_vuv)   phoneme stack `t`, duration and pitch recurrences — the parameters of opt_t
          cond()  -> conditioning [B, F, 80]                  phoneme stack `g`, conditioning recurrence (target pitch as input) — part of opt_g
     They share inputs only (no parameter, no activation), so a caller may run them on different streams."""
-    if getattr(lang, '_use_cond', False):
-        raise NotImplementedError("training with external conditioning ('fasttext:..' / 'hf:..') is not built: the encoders cannot be "
-                                  "downloaded here and the conditioning branch (modules.py:963-990) is inference-only; use conditioning=None")
     dev = lang._get_device()
     x_char, x_speaker = _h2d(X, 'x_char', dev), _h2d(X, 'x_speaker', dev)
 
     _require_device(x_char, 'languasito_forward_train')
     embed, linear, cnn = _text_ops(lang)
+    use_cond = bool(getattr(lang, '_use_cond', False))
+    x_words = p2w_dev = None
+    if use_cond:
+        # external conditioning (modules.py:932-940, 979-988): per-word vectors in ('fasttext': a local table through the collate, 'hf': per-word
+        # encoder states the caller supplies), a BiLSTM of each stack over them, and every phoneme row extended by its word's state
+        from .text_autograd import PhoneRowsAssembleFn, checked_phon2word
+        if X.get('x_tok_ids') is not None or X.get('x_words') is None:
+            raise NotImplementedError('training with external conditioning needs X["x_words"] ([B, Nw, %d] vectors per word: CubeganCollate(..., word_vectors=) '
+                                      "for 'fasttext:..', per-word encoder states for 'hf:..'); the pretrained encoders themselves are not part of this "
+                                      'build (modules.py:933-934, _expand_i_hf)' % lang._lm_t.input_size)
+        if tuple(X['x_words'].shape[::2]) != (x_char.shape[0], lang._lm_t.input_size) or tuple(X['x_phon2word'].shape) != tuple(x_char.shape):
+            raise _lib.TTSCError('languasito_forward_train: x_words %s / x_phon2word %s do not fit x_char %s and the word encoders\' input size %d' %
+                                 (tuple(X['x_words'].shape), tuple(X['x_phon2word'].shape), tuple(x_char.shape), lang._lm_t.input_size))
+        p2w_dev = checked_phon2word(X['x_phon2word'], X['x_words'].shape[1], 'languasito_forward_train').to(dev, non_blocking=True)
+        x_words = _h2d(X, 'x_words', dev).float()
 
     def stack(which):
         h = embed(getattr(lang, '_phon_emb_' + which), x_char).permute(0, 2, 1)
         h = cnn('_char_cnn_' + which, h)
         h = lstm_forward_train(getattr(lang, '_char_rnn_' + which), h.permute(0, 2, 1))
         spk = embed(getattr(lang, '_speaker_emb_' + which), x_speaker)
+        if use_cond:
+            # one launch for the whole row (and one for its three gradients, summed in a fixed order: csrc/train_ops.hip::phone_rows_assemble_bwd_kernel)
+            return PhoneRowsAssembleFn.apply(h, spk, lstm_forward_train(getattr(lang, '_lm_' + which), x_words), p2w_dev)
         return torch.cat([h, spk.repeat(1, h.shape[1], 1)], dim=-1)
 
     alignments = X['y_frame2phone']
@@ -229,7 +246,8 @@ def _languasito_branches(lang, X):
         g = lstm_forward_train(lang._cond_rnn, torch.cat([g[:, :m], pitch_in[:, :m]], dim=-1))
         return linear(g, lang._cond_output.linear_layer.weight, lang._cond_output.linear_layer.bias)
 
-    text.shared_inputs = cond.shared_inputs = [x_char, x_speaker, idx_dev, pitch_in]   # allocated here, read by both closures
+    shared = [x_char, x_speaker, idx_dev, pitch_in] + ([x_words, p2w_dev] if use_cond else [])
+    text.shared_inputs = cond.shared_inputs = shared    # allocated here, read by both closures
     return text, cond
 
 
