@@ -809,6 +809,23 @@ int ttsc_g2p_train_forward(const ttsc_g2p_train_args* args, void* stream);
 int ttsc_g2p_train_backward(const ttsc_g2p_train_args* args, void* stream);
 int ttsc_dropout_scale(const float* x_dev, int64_t n, float p, const float* mask_dev, uint64_t seed, int32_t stream_id, float* y_dev, void* stream);
 
+/* Pitch tracker of the corpus importer (csrc/pitch.hip; io_utils/pitch.py; the float64 statement is tests/pitch_reference.py): a single-rate RAPT
+ * (Talkin 1995) without the decimated first pass and without the spectral-stationarity term.  Two launches for a batch of ragged utterances.
+ *   nccf    x [B, Lmax] float32 in [-1, 1], len [B]; F_b = len[b] / hop frames, Fmax = Lmax / hop rows per utterance; window n, lags kmin .. kmax
+ *           (K = kmax - kmin + 1, kmax >= kmin + 2).  Frame t starts at t * hop, samples at or past len[b] read as zero, the mean of its n + kmax
+ *           samples is removed, phi[k] = sum_{j<n} s[j] s[j+k] / sqrt(e_0 e_k + A).  Writes the 20 largest peaks with phi >= 0.3 max phi, largest
+ *           first, ties to the smaller lag, each refined by a parabola: cand_lag / cand_val [B, Fmax, 20] (unused slots 0), ncand [B, Fmax],
+ *           maxphi [B, Fmax], rms [B, Fmax] of the window, and phi [B, Fmax, K] when phi_dev is not NULL.  Rows t >= F_b are written as zeros.
+ *   track   Viterbi over 21 states per frame (candidates 0 .. ncand - 1, state 20 = unvoiced) from those tables (or injected ones) for nframes[b]
+ *           frames, ties to the lowest state; f0 [B, Fmax] = sample_rate / lag of the chosen candidate, 0 where unvoiced and past nframes[b].
+ *           workspace: ttsc_pitch_track_workspace_bytes(B, Fmax) bytes of back-pointers. */
+int ttsc_pitch_nccf(const float* x_dev, const int32_t* len_dev, int32_t B, int64_t Lmax, int32_t hop, int32_t n, int32_t kmin, int32_t kmax,
+                    float* cand_lag_dev, float* cand_val_dev, int32_t* ncand_dev, float* maxphi_dev, float* rms_dev, float* phi_dev, void* stream);
+size_t ttsc_pitch_track_workspace_bytes(int32_t B, int64_t Fmax);
+int ttsc_pitch_track(const float* cand_lag_dev, const float* cand_val_dev, const int32_t* ncand_dev, const float* maxphi_dev, const float* rms_dev,
+                     const int32_t* nframes_dev, int32_t B, int64_t Fmax, int32_t kmax, float sample_rate, void* workspace_dev, size_t workspace_bytes,
+                     float* f0_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
