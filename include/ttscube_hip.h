@@ -826,6 +826,16 @@ int ttsc_pitch_track(const float* cand_lag_dev, const float* cand_val_dev, const
                      const int32_t* nframes_dev, int32_t B, int64_t Fmax, int32_t kmax, float sample_rate, void* workspace_dev, size_t workspace_bytes,
                      float* f0_dev, void* stream);
 
+/* Rational-rate polyphase FIR resampler of the audio readers (csrc/resample.hip; io_utils/resample.py; the float64 statement is
+ * tests/resample_reference.py): scipy.signal.resample_poly(x, up, down) with its default Kaiser-5 filter, for a ragged batch in one launch.
+ *   x [B, Lmax] float32, len [B] (clamped to [0, Lmax]); up, down coprime, both in [1, 1024]; half = 10 max(up, down), K = ceil((2 half + 1) / up).
+ *   taps: the filter h[0 .. 2 half] (already multiplied by up) padded with zeros to ntaps = up * K4 floats, K4 = K rounded up to a multiple of 4.
+ *   y [B, Omax], Omax >= ceil(Lmax up / down): row b holds y[n] = sum_i x[i] h[n down - i up + half] over |n down - i up| <= half for
+ *   n < ceil(len[b] up / down), zeros behind; peak [B] = max |y| of the row (0 for an empty row).  fp32 sums in an order that depends on (n, up,
+ *   down) alone: a row has the same bits alone and in any batch.  Index arithmetic is 64-bit. */
+int ttsc_resample_poly(const float* x_dev, const int32_t* len_dev, int32_t B, int64_t Lmax, int32_t up, int32_t down, const float* taps_dev,
+                       int64_t ntaps, float* y_dev, int64_t Omax, float* peak_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

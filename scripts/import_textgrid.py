@@ -1,6 +1,7 @@
 """Import a folder of Montreal Forced Aligner output (`<name>.wav` + `<name>.TextGrid`) into the processed corpus the trainers read:
 `<output-folder>/{train,dev}/<id>.{json,mgc,pitch,wav}`.  The flags of the reference's scripts/import_textgrid.py, plus --output-folder, --batch
-(utterances per GPU call of the spectrogram and of the pitch tracker) and --device.
+(utterances per GPU call of the spectrogram and of the pitch tracker), --device and --gpu-resample (files that are not at --sample-rate are
+converted by the HIP resampler instead of scipy on the host).
 
     python scripts/import_textgrid.py --input-folder aligned/ --speaker anna --prefix ANNA --dev-ratio 0.01
     python scripts/train_textcoder.py ...      # reads data/processed/{train,dev}"""
@@ -25,6 +26,8 @@ def main(argv=None):
     parser.add_option('--original-text', dest='original_text', help='Used to fetch context from')
     parser.add_option('--batch', type='int', dest='batch', default=32, help='Utterances per GPU call (default=32)')
     parser.add_option('--device', dest='device', default='cuda:0', help='Device of the spectrogram and the pitch tracker (default=cuda:0)')
+    parser.add_option('--gpu-resample', action='store_true', dest='gpu_resample', default=False,
+                      help='Bring the files to --sample-rate on the GPU (io_utils/resample.py) instead of with scipy on the host')
     params, _ = parser.parse_args(sys.argv[1:] if argv is None else argv)
     if not params.input_folder:
         parser.print_help()
@@ -32,8 +35,13 @@ def main(argv=None):
     if params.batch < 1:
         parser.error('--batch must be at least 1')
     from ttscube_amd.io_utils.corpus_import import import_dataset
+    resampler = None
+    if params.gpu_resample:
+        from ttscube_amd.io_utils.resample import Resampler
+        resampler = Resampler(params.device)
     import_dataset(params.input_folder, params.output_folder, dev_ratio=params.dev_ratio, speaker=params.speaker, sample_rate=params.sample_rate,
-                   hop_size=params.hop_size, prefix=params.prefix, original_text=params.original_text, batch=params.batch, device=params.device)
+                   hop_size=params.hop_size, prefix=params.prefix, original_text=params.original_text, batch=params.batch, device=params.device,
+                   resampler=resampler)
     return 0
 
 

@@ -9,7 +9,8 @@ state_dicts), <base>.last (CubenetVocoder state_dict, prefixes _wavernn_hr. / _w
 
 Data: `--train-folder` / `--dev-folder` hold .wav files; io_utils.io_vocoder.VocoderDataset reads them exactly as the reference's
 (normalise to 0.98 peak, low-rate copy, log10-mel — computed on the GPU here —, `data/cache` files, random hop-aligned crops
-of `--maximum-segment-size` samples).  Every rank trains on its own slice of exactly ceil(N / world) files (`rank_shard`: wrap-padded,
+of `--maximum-segment-size` samples; `--precompute-cache` fills those cache files in batches before the first epoch instead of file by file
+inside it).  Every rank trains on its own slice of exactly ceil(N / world) files (`rank_shard`: wrap-padded,
 so all ranks run the same number of steps and gradient exchanges), loaded by `--num-workers` background threads; `.lr.best` / `.hr.best` are
 selected on the dev-set losses (train_vocoder.py:36-59 of the reference).  `--synthetic N` ignores the folders and uses N seeded
 synthetic items per rank; it must be asked for explicitly — a missing or empty folder is an error."""
@@ -69,6 +70,13 @@ def _datasets(params, rank, world):
     dev = VocoderDataset(params.dev_folder, max_segment_size=params.maximum_segment_size, random_start=False, **kw)
     if len(train) == 0 or len(dev) == 0:
         raise SystemExit('no usable .wav files under %s / %s' % (params.train_folder, params.dev_folder))
+    if params.precompute_cache:
+        # rank 0 fills the cache in batches (HIP resampler, one spectrogram call per batch); the others wait and then find every file cached
+        if rank == 0:
+            for ds in (train, dev):
+                sys.stdout.write('precomputed the cache files of %d files\n' % ds.precompute(device='cuda:%d' % int(os.environ.get('LOCAL_RANK', '0'))))
+        if world > 1:
+            dist.barrier()
     return _RankSlice(train, rank, world), dev
 
 
@@ -159,5 +167,7 @@ if __name__ == '__main__':
     p.add_argument('--output', dest='output', default='mol', help='mol|gm|beta|mulaw|raw (cube/networks/loss.py)')
     p.add_argument('--resume', dest='resume', action='store_true')
     p.add_argument('--epochs', type=int, default=1)
+    p.add_argument('--precompute-cache', dest='precompute_cache', action='store_true',
+                   help='fill data/cache for both folders in batches on the GPU before the first epoch (VocoderDataset.precompute)')
     p.add_argument('--synthetic', type=int, default=0, help='ignore the folders and train on N seeded synthetic items per rank')
     _train(p.parse_args())

@@ -189,9 +189,10 @@ def _write_item(folder, item, seg, mel, pitch, sample_rate):
         json.dump(item, f)
 
 
-def import_audio(dataset, paths, output_folder, sample_rate, hop_size, prefix, batch=32, device='cuda:0', fmin=60, fmax=400):
+def import_audio(dataset, paths, output_folder, sample_rate, hop_size, prefix, batch=32, device='cuda:0', fmin=60, fmax=400, resampler=None):
     """dataset: item dicts (sorted here by file name; ids are '<prefix>_<index:08d>' in that order), paths: orig_filename -> path without
-    extension.  -> number of utterances written"""
+    extension; resampler: an io_utils.resample.Resampler brings the files to sample_rate on the GPU (default: scipy on the host).
+    -> number of utterances written"""
     from .audio import load_wav
     from .pitch import PitchTracker
     from .vocoder import MelVocoder
@@ -226,7 +227,7 @@ def import_audio(dataset, paths, output_folder, sample_rate, hop_size, prefix, b
     for index, item in enumerate(dataset):
         item['id'] = '{0}_{1:08d}'.format(prefix, index)
         if loaded != item['orig_filename']:
-            wav, _ = load_wav(paths[item['orig_filename']] + '.wav', sample_rate)
+            wav, _ = load_wav(paths[item['orig_filename']] + '.wav', sample_rate, resampler=resampler)
             loaded = item['orig_filename']
         seg = np.asarray(wav[int(item['orig_start'] * per_ms):int(item['orig_end'] * per_ms)], dtype=np.float32)
         peak = float(np.max(np.abs(seg))) if seg.size else 0.0
@@ -244,7 +245,7 @@ def import_audio(dataset, paths, output_folder, sample_rate, hop_size, prefix, b
 
 
 def import_dataset(input_folder, output_folder='data/processed', dev_ratio=0.001, speaker='none', sample_rate=24000, hop_size=240, prefix='FILE',
-                   original_text=None, batch=32, device='cuda:0'):
+                   original_text=None, batch=32, device='cuda:0', resampler=None):
     """-> (utterances written to train, to dev)"""
     print('Search input folder for valid files')
     bases = find_pairs(input_folder)
@@ -273,5 +274,5 @@ def import_dataset(input_folder, output_folder='data/processed', dev_ratio=0.001
     counts = []
     for name, part in (('train', train), ('dev', dev)):
         print('Processing {0}set'.format(name))
-        counts.append(import_audio(part, paths, os.path.join(output_folder, name), sample_rate, hop_size, prefix, batch=batch, device=device))
+        counts.append(import_audio(part, paths, os.path.join(output_folder, name), sample_rate, hop_size, prefix, batch=batch, device=device, resampler=resampler))
     return tuple(counts)
