@@ -836,6 +836,25 @@ int ttsc_pitch_track(const float* cand_lag_dev, const float* cand_val_dev, const
 int ttsc_resample_poly(const float* x_dev, const int32_t* len_dev, int32_t B, int64_t Lmax, int32_t up, int32_t down, const float* taps_dev,
                        int64_t ntaps, float* y_dev, int64_t Omax, float* peak_dev, void* stream);
 
+/* Timeline mixer of StoryCube (csrc/story.hip; io_utils/story_mix.py; ttscube_amd/story.py; the restatement is tests/story_reference.py): the
+ * narrated track of cube/story.py in one launch.  out[j], j < n, is timeline sample t = t0 + j:
+ *     s = trunc(fl32(speech[seg_src[p] + (t - seg_dst[p])] * 32767))   where seg_dst[p] <= t < seg_dst[p] + seg_len[p], else 0
+ *     out[j] = int16(trunc(fl32(fl32(fl32(music[t % M] * music_gain) * music_scale) + s)))
+ * three float32 operations rounded one by one (never fused), truncation toward zero: the bits of the reference's per-sample loop.  A sum outside
+ * the int16 range (undefined in the reference) saturates to [-32768, 32767] and adds 1 to *clipped_dev when that is not NULL (an integer count:
+ * the same value in any order; the caller zeroes it).  Every out[j] is written exactly once; P == 0 is the music bed alone; n == 0 launches nothing.
+ *   speech   packed float32 waveforms in (-1, 1); only the elements inside a segment are read
+ *   seg_*    [P] int64 ON THE DEVICE: first sample in speech, length >= 0, first sample on the timeline; ascending and non-overlapping
+ *            (seg_dst[p] + seg_len[p] <= seg_dst[p + 1]; empty and adjacent segments are fine).  All index arithmetic is 64-bit.
+ * Checked here, before any launch (nonzero status, the last-error text set): M < 1, negative P / n / t0, t0 + n beyond 64 bits, a NULL pointer with
+ * a nonzero size, misaligned out / clipped.  The segment tables live on the device and are NOT read back here: negative lengths, unsorted or
+ * overlapping segments and segments beyond the speech buffer are refused by the caller that still holds host copies
+ * (io_utils/story_mix.py::mix_timeline with host tables raises the same error before the launch); tables handed over as device tensors are
+ * the caller's promise.  A table that breaks it gives unspecified samples but reads nothing outside [seg_src[p], seg_src[p] + seg_len[p]). */
+int ttsc_story_mix(const float* speech_dev, const int64_t* seg_src_dev, const int64_t* seg_len_dev, const int64_t* seg_dst_dev, int32_t P,
+                   const float* music_dev, int64_t M, float music_gain, float music_scale, int64_t t0, int64_t n, int16_t* out_dev,
+                   int64_t* clipped_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,12 +148,38 @@ class TTSCube:
         padded batches of up to `max_batch`; ragged lengths are handled inside the kernels (masked BiLSTMs), so each
         result equals the single-sentence call — with word conditioning too: the collate's word counts (x_words_len) stop the word BiLSTMs at each
         sentence's own last word."""
+        out = [None] * len(texts)
+
+        def collect(ids, wav, lens):
+            wav = wav.detach().cpu().numpy()
+            for j, i in enumerate(ids):
+                out[i] = np.asarray(wav[j, 0, :lens[j]] * 32767, dtype=np.int16)
+
+        self._run_groups(texts, speaker, max_batch, collect)
+        return out
+
+    def _synthesize_batch_device(self, texts, speaker='none', max_batch=64):
+        """`synthesize_batch` without the copy to the host: -> list of 1-D float32 device tensors in (-1, 1), in input order, each trimmed to its
+        own sample count (views of the padded batches).  `np.asarray(t.cpu().numpy() * 32767, dtype=np.int16)` of an entry is that sentence's
+        `synthesize_batch` result.  For callers that go on working on the device (story.StoryCube)."""
+        out = [None] * len(texts)
+
+        def collect(ids, wav, lens):
+            wav = wav.detach()
+            for j, i in enumerate(ids):
+                out[i] = wav[j, 0, :lens[j]]
+
+        self._run_groups(texts, speaker, max_batch, collect)
+        return out
+
+    def _run_groups(self, texts, speaker, max_batch, collect):
+        """the grouping and the inference behind synthesize_batch: `collect(ids, wav [B, 1, L] on the device, sample counts)` is called once per
+        padded batch, ids = the positions of its sentences in `texts`; after a tripped range guard it is called again for every batch."""
         speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
         # a front-end with a `batch` method (io_text.Text2FeatBlizzard) phonemizes the whole list in one padded call
         feats = self._text2feat.batch(list(texts)) if hasattr(self._text2feat, 'batch') else [None] * len(texts)
         ex = [self._example(t, s, f) for t, s, f in zip(texts, speakers, feats)]
         order = sorted(range(len(ex)), key=lambda i: len(ex[i]['meta']['phones']))
-        out = [None] * len(ex)
         groups = [order[s:s + max_batch] for s in range(0, len(order), max_batch)]
 
         def feed():
@@ -164,11 +190,9 @@ class TTSCube:
                         X[key] = X[key].to(self._model.get_device())
                 yield X
 
-        def collect(results):
+        def collect_all(results):
             for ids, (wav, lens) in zip(groups, results):
-                wav = wav.detach().cpu().numpy()
-                for j, i in enumerate(ids):
-                    out[i] = np.asarray(wav[j, 0, :lens[j]] * 32767, dtype=np.int16)
+                collect(ids, wav, lens)
 
         with torch.no_grad():
             if len(groups) > 1:
@@ -176,13 +200,12 @@ class TTSCube:
                 # per-batch results are the ones `inference` gives.  The pipeline runs the range guard deferred; a batch that left the calibrated
                 # range raises there, and the whole list is then redone batch by batch with the self-repairing synchronous guard.
                 try:
-                    collect(self._model.inference_pipelined(feed()))
-                    return out
+                    collect_all(self._model.inference_pipelined(feed()))
+                    return
                 except _lib.TTSCError as e:
                     if 'check="sync"' not in str(e):
                         raise
-            collect(self._model.inference(X, return_lengths=True) for X in feed())
-        return out
+            collect_all(self._model.inference(X, return_lengths=True) for X in feed())
 
     @staticmethod
     def shard(items, rank, world_size):
