@@ -855,6 +855,38 @@ int ttsc_story_mix(const float* speech_dev, const int64_t* seg_src_dev, const in
                    const float* music_dev, int64_t M, float music_gain, float music_scale, int64_t t0, int64_t n, int16_t* out_dev,
                    int64_t* clipped_dev, void* stream);
 
+/* Complex STFT, inverse STFT and the Griffin-Lim projection on a radix-4 Stockham FFT held in LDS (csrc/stft_fft.hip; io_utils/stft.py; the float64
+ * statement is tests/griffinlim_reference.py): the rest of MelVocoder (cube/io_utils/vocoder.py:42-52,69-75,100-124), librosa's conventions:
+ * periodic Hann of length n_fft, centred frames over n_fft/2 samples of reflect padding, NB = n_fft/2 + 1 bins, F = 1 + L // hop frames, the
+ * inverse returns hop (F - 1) samples.  n_fft in {256, 512, 1024, 2048}, 1 <= hop <= n_fft, else TTSC_EINVAL.
+ *   Ragged batches: B rows of frames[b] frames each in buffers [B, Fmax, ...] / [B, L...]; frames_host is the caller's host copy of
+ *   frames_dev (int32 [B]; both NULL: every row has Fmax frames) and serves the argument checks: every row needs 1 <= frames[b] <= Fmax and
+ *   hop (frames[b] - 1) >= n_fft/2 + 1 samples (reflect padding), else TTSC_EINVAL.  Buffer rows at or beyond a row's own frames / samples are
+ *   never read and are written as zeros; a row's bits do not depend on the batch around it.
+ *   tables_dev: 3 n_fft floats — n_fft (re, im) twiddles, entry Ns + k = exp(-2 pi i k / (2 Ns)) for Ns = 1, 2 .. n_fft/2, k < Ns (entry 0
+ *   unused), then the window; built in float64 and rounded once (io_utils/stft.py::tables).
+ *   ttsc_stft_reflect_pad   y [B, Lmax] with len[b] samples (n_fft/2 + 1 .. Lmax) -> out [B, Lpad], Lpad >= Lmax + n_fft: numpy's reflect
+ *                           padding by n_fft/2, zeros behind len[b] + n_fft
+ *   ttsc_stft_analyze       padded signal [B, Lpad], Lpad >= hop (Fmax - 1) + n_fft -> spectrum [B, Fmax, NB] of interleaved (re, im); frame f
+ *                           is read in place at f hop
+ *   ttsc_stft_synthesize    spectrum [B, Fmax, NB] -> frames [B, Fmax, n_fft]: the real inverse transform / n_fft, times the window; the
+ *                           imaginary parts of bins 0 and n_fft/2 are ignored
+ *   ttsc_stft_project       one Griffin-Lim half step in one launch: padded signal, magnitude [B, Fmax, NB] -> frames [B, Fmax, n_fft] of
+ *                           |mag| (re, im) / |(re, im)| of the signal's own STFT ((0, 0) has phase (1, 0)); the spectrum never leaves LDS
+ *   ttsc_stft_overlap_add   frames [B, Fmax, n_fft] -> sum of the frames at hop, divided by the sum of the squared window where that exceeds
+ *                           FLT_MIN (one thread per sample, ascending frames).  padded = 0: the audio [B, ldo = hop (Fmax - 1)];
+ *                           padded = 1: the reflect-padded audio [B, ldo = hop (Fmax - 1) + n_fft] that the next ttsc_stft_project reads */
+int ttsc_stft_reflect_pad(const float* y_dev, const int32_t* len_host, const int32_t* len_dev, int32_t B, int64_t Lmax, int32_t n_fft,
+                          float* out_dev, int64_t Lpad, void* stream);
+int ttsc_stft_analyze(const float* sig_dev, int64_t Lpad, const int32_t* frames_host, const int32_t* frames_dev, int32_t B, int32_t Fmax,
+                      int32_t n_fft, int32_t hop, const float* tables_dev, float* spec_dev, void* stream);
+int ttsc_stft_synthesize(const float* spec_dev, const int32_t* frames_host, const int32_t* frames_dev, int32_t B, int32_t Fmax, int32_t n_fft,
+                         int32_t hop, const float* tables_dev, float* frames_out_dev, void* stream);
+int ttsc_stft_project(const float* sig_dev, int64_t Lpad, const float* mag_dev, const int32_t* frames_host, const int32_t* frames_dev,
+                      int32_t B, int32_t Fmax, int32_t n_fft, int32_t hop, const float* tables_dev, float* frames_out_dev, void* stream);
+int ttsc_stft_overlap_add(const float* frames_in_dev, const int32_t* frames_host, const int32_t* frames_dev, int32_t B, int32_t Fmax,
+                          int32_t n_fft, int32_t hop, const float* tables_dev, int32_t padded, float* out_dev, int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,11 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     'ttsc_story_mix': (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
+    'ttsc_stft_reflect_pad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'ttsc_stft_analyze': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3),
+    'ttsc_stft_synthesize': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
+    'ttsc_stft_project': (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
+    'ttsc_stft_overlap_add': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 
