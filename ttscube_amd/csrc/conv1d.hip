@@ -15,6 +15,7 @@
 // that hits L2; both streams are software-pipelined explicitly (see conv_mfma_kernel).  Epilogue fuses bias, residual
 // add, scaling, tanh, the running sum over residual blocks and — for data-gradient launches — the leaky-relu derivative.
 // The split-precision kernels further down (conv_f16x3_kernel, respair32_f16x3_kernel) are the default for the generator.
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -43,7 +44,22 @@ namespace ttsc {
 // 4 / 8 / 12 barriers per two chunks for K = 3 / 7 / 11 instead of 6 / 14 / 22: 42.84-42.93 ms per forward against 42.96-43.03 with two slots in
 // the product build, i.e. inside the noise, and 30-55 % SLOWER in the -DTTSC_ABLATE build of the very same source (profiles/r05_wg_timeline_slots.log) —
 // a schedule that fragile is not worth 0.1 ms.)
-template <int C, int K, int D>
+// LEAN (wide and tall kernels; host switch TTSC_CONV_LEAN, default on): the staging pass carries no address arithmetic and no padding selects.
+//   * the eight loads of a staging item go through ONE raw buffer descriptor per workgroup (its utterance's input: base x + b*C*Lin, C*Lin*4 bytes,
+//     stride 0) with ONE 32-bit per-lane byte offset; the channel row is the instruction's scalar offset (wave-uniform: scalar adds, no
+//     v_lshl_add_u64 per load);
+//   * a raw buffer load returns 0 for an offset outside the descriptor, so lanes whose position lies outside [0, lin) — and the lanes that only
+//     feed the dump slot — carry LEAN_OOB as their offset and the per-value `xok ? v * scale : 0` select goes: 0.0f * in_scale (finite, positive:
+//     checked by the host), the leaky-relu and the split of +0 give the bits the select gave.  Whether the hardware's range check adds the scalar
+//     offset or not does not matter: the host requires C*Lin*4 < 2^31, so LEAN_OOB alone is beyond the range and LEAN_OOB + row offset does not
+//     wrap, while every real access (per-lane offset + row offset) ends below C*Lin*4 either way.
+// LEAN = false is the kernel as it was (also taken when the input is too large for 32-bit byte offsets).
+static constexpr unsigned LEAN_OOB = 0x80000000u;
+__device__ __forceinline__ float lean_load(__amdgpu_buffer_rsrc_t rs, unsigned voff, int soff) {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, soff, 0));
+}
+
+template <int C, int K, int D, bool LEAN>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_wide_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int WM = 2, WN = 2;                   // 128 output channels x 256 positions per workgroup (grid.y = C / 128)
@@ -216,11 +232,20 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_wide_kernel(ConvArgs a) {
         xoff[e] = (unsigned)(h * 8 * a.Lin + pc);   // channel half folded into the offset
         // lanes beyond the window write to a dump slot behind the planes (no divergent branch around the LDS stores)
         xslot[e] = (p < SPAN && i < 2 * SPANP) ? (h * 2) * SPAN + p : 4 * SPAN;
+        if (LEAN) xoff[e] = (xok[e] && xslot[e] < 4 * SPAN) ? xoff[e] * 4u : LEAN_OOB;   // byte offset, or one no access can have: the load returns 0
     }
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, LEAN ? C * a.Lin * 4 : 0, 0x00020000);
+    const int xrow = a.Lin * 4;   // bytes per channel row
     auto x_issue_item = [&](int e, int c) __attribute__((always_inline)) {
-        const float* rc = xb + (size_t)(c * 16) * a.Lin;
+        if constexpr (LEAN) {
+            const int s0 = c * 16 * xrow;   // the chunk's first row: scalar, like the seven that follow
 #pragma unroll
-        for (int ch = 0; ch < 8; ++ch) xr[e][ch] = rc[(size_t)ch * a.Lin + xoff[e]];
+            for (int ch = 0; ch < 8; ++ch) xr[e][ch] = lean_load(xrs, xoff[e], s0 + ch * xrow);
+        } else {
+            const float* rc = xb + (size_t)(c * 16) * a.Lin;
+#pragma unroll
+            for (int ch = 0; ch < 8; ++ch) xr[e][ch] = rc[(size_t)ch * a.Lin + xoff[e]];
+        }
     };
     auto x_commit_item = [&](int e, half8* buf) __attribute__((always_inline)) {
         // (hi, lo) split of the 8 channels, pairwise: cvt_pk + two fma_mix + cvt_pk per pair (conv_internal.hpp::split2_f16; same bits as the
@@ -229,7 +254,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_wide_kernel(ConvArgs a) {
         u32x4 uh, ul;
 #pragma unroll
         for (int ch = 0; ch < 8; ch += 2) {
-            float v0 = xok[e] ? xr[e][ch] * a.in_scale : 0.f, v1 = xok[e] ? xr[e][ch + 1] * a.in_scale : 0.f;
+            // (LEAN: a lane outside the data loaded 0.0f, see LEAN_OOB)
+            float v0 = (LEAN || xok[e]) ? xr[e][ch] * a.in_scale : 0.f, v1 = (LEAN || xok[e]) ? xr[e][ch + 1] * a.in_scale : 0.f;
             v0 = fmaxf(v0, v0 * a.in_slope);
             v1 = fmaxf(v1, v1 * a.in_slope);
             unsigned h, l;
@@ -756,8 +782,8 @@ static int launch_f16_t(const ConvArgs& a, int B, hipStream_t s) {
     return TTSC_OK;
 }
 
-template <int C, int K, int D>
-static int launch_f16_wide(const ConvArgs& a0, int B, hipStream_t s) {
+template <int C, int K, int D, bool LEAN>
+static int launch_f16_wide_l(const ConvArgs& a0, int B, hipStream_t s) {
     constexpr int NT = 256;
     constexpr int SPAN = NT + (K - 1) * D;
     dim3 grid((unsigned)ceil_div(a0.Lout, NT), (unsigned)(C / 128), (unsigned)B);
@@ -773,14 +799,19 @@ static int launch_f16_wide(const ConvArgs& a0, int B, hipStream_t s) {
     static const int epi_env = getenv("TTSC_CONV_EPI_PREFETCH") ? atoi(getenv("TTSC_CONV_EPI_PREFETCH")) : 1;
     a.epi_prefetch = (epi_env && !a.gate && a.out_act == TTSC_ACT_NONE && a.Cout == C && (size_t)B * C * a.Lout < (1ull << 32)) ? 1 : 0;   // (32-bit element offsets)
     constexpr size_t lds = (size_t)2 * (4 * SPAN + 2) * 16 + (size_t)2 * (2 * 2 * 2 * 64) * 16;   // activations + 2 weight slots
-    if (int rc = ensure_full_lds((const void*)conv_f16x3_wide_kernel<C, K, D>)) return rc;   // once per (device, kernel)
-    hipLaunchKernelGGL((conv_f16x3_wide_kernel<C, K, D>), grid, dim3(256), lds, s, a);
+    if (int rc = ensure_full_lds((const void*)conv_f16x3_wide_kernel<C, K, D, LEAN>)) return rc;   // once per (device, kernel)
+    hipLaunchKernelGGL((conv_f16x3_wide_kernel<C, K, D, LEAN>), grid, dim3(256), lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("conv_f16x3_wide_kernel launch failed: %s", hipGetErrorString(e));
         return TTSC_EHIP;
     }
     return TTSC_OK;
+}
+
+template <int C, int K, int D>
+static int launch_f16_wide(const ConvArgs& a, int B, hipStream_t s) {
+    return a.lean ? launch_f16_wide_l<C, K, D, true>(a, B, s) : launch_f16_wide_l<C, K, D, false>(a, B, s);
 }
 
 
@@ -792,7 +823,11 @@ static int launch_f16_wide(const ConvArgs& a0, int B, hipStream_t s) {
 // same 24 MFMAs per 12 fragment reads as the wide kernel), so the window is staged 5 / 3 times instead of 20 / 12, on the wide kernel's
 // skeleton: weights by LDS-DMA one tap ahead, activations double-buffered, conversion of chunk c+1 spread over the last taps of chunk c.
 // (MI, NJ) = (4, 2): 256 rows x 128 positions (ups.0: 1280 rows); (2, 4): 128 rows x 256 positions (ups.1: 384 rows = 3 tiles instead of 6).
-template <int CIN, int J, int MI, int NJ>
+// LEAN (see conv_f16x3_wide_kernel): the staging loads go through the buffer descriptor, and a workgroup whose row tile is a phase without the
+// last tap (phase r has ceil((K - r) / stride) real taps: 4 3 3 3 3 of J = 4 for ups.0, 6 5 5 of J = 6 for ups.1; the packers fill tap J - 1 of
+// the others with zero weights) runs J - 1 taps per chunk: no weight LDS-DMA, no fragment reads, no 24 MFMAs and no barrier for the zero tap.
+// The real taps and their order are unchanged, so every finite output keeps its bits (a zero tap only ever added +0 to a sum that started at +0).
+template <int CIN, int J, int MI, int NJ, bool LEAN>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int WM = 2, WN = 2, NT = WN * NJ * 32;
@@ -801,7 +836,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
     constexpr int BUFSZ = 4 * SPAN + 2;
     constexpr int NCHUNK = CIN / 16;
     constexpr int AITEMS = WM * MI * 2 * 64;        // weight items of one (tap, chunk) for the workgroup's 256 rows (16 KB)
-    static_assert(J % 2 == 0 && NCHUNK % 2 == 0, "slot parity: an even number of taps per chunk, chunks in pairs");
+    static_assert(NCHUNK % 2 == 0, "slot parity: chunks in pairs (two chunks of NTAPS taps each end on the slot they started on)");
     half8* Xp = reinterpret_cast<half8*>(smem_raw);   // [2 buffers][plane (h, pl)][SPAN]
     half8* Aw = Xp + 2 * BUFSZ;                       // [2 slots][AITEMS]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -841,11 +876,14 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
     const float* xb = a.x + (size_t)b * CIN * a.Lin;
     const int lo = q0 - (J - 1);                      // x position of LDS column 0 (tap j reads column (q - q0) + J - 1 - j)
     const half8* wsrc = reinterpret_cast<const half8*>(a.wph) + (size_t)cotg * 128 + lane;
+    // (LEAN: the wave index as a scalar, so that the block addresses of the weight LDS-DMA are scalar arithmetic; as a vector value its 64-bit
+    // copy was live across the tap loops and, with two of them in the kernel, went to scratch in the <256, 6, 2, 4> instantiation)
+    const int wave_s = LEAN ? __builtin_amdgcn_readfirstlane(wave) : wave;
     auto stage_A = [&](int c, int j, int slot) __attribute__((always_inline)) {
         const half8* wj = wsrc + (size_t)(j * NCHUNK + c) * ((size_t)cotN * 128);
 #pragma unroll
         for (int i = 0; i < AITEMS / 64 / 4; ++i) {
-            const int blk = wave + i * 4;
+            const int blk = wave_s + i * 4;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wj + blk * 64),
                                              (__attribute__((address_space(3))) void*)(Aw + slot * AITEMS + blk * 64), 16, 0, 0);
         }
@@ -867,11 +905,20 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
         pc = pc < 0 ? 0 : pc;
         xoff[e] = (unsigned)(h * 8 * a.Lin + pc);
         xslot[e] = (p < SPAN && i < 2 * SPANP) ? (h * 2) * SPAN + p : 4 * SPAN;
+        if (LEAN) xoff[e] = (xok[e] && xslot[e] < 4 * SPAN) ? xoff[e] * 4u : LEAN_OOB;   // byte offset, or one no access can have: the load returns 0
     }
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, LEAN ? CIN * a.Lin * 4 : 0, 0x00020000);
+    const int xrow = a.Lin * 4;   // bytes per channel row
     auto x_issue_item = [&](int e, int c) __attribute__((always_inline)) {
-        const float* rc = xb + (size_t)(c * 16) * a.Lin;
+        if constexpr (LEAN) {
+            const int s0 = c * 16 * xrow;
 #pragma unroll
-        for (int ch = 0; ch < 8; ++ch) xr[e][ch] = rc[(size_t)ch * a.Lin + xoff[e]];
+            for (int ch = 0; ch < 8; ++ch) xr[e][ch] = lean_load(xrs, xoff[e], s0 + ch * xrow);
+        } else {
+            const float* rc = xb + (size_t)(c * 16) * a.Lin;
+#pragma unroll
+            for (int ch = 0; ch < 8; ++ch) xr[e][ch] = rc[(size_t)ch * a.Lin + xoff[e]];
+        }
     };
     auto x_commit_item = [&](int e, half8* buf) __attribute__((always_inline)) {
         // (hi, lo) split of the 8 channels, pairwise: cvt_pk + two fma_mix + cvt_pk per pair (conv_internal.hpp::split2_f16; same bits as the
@@ -880,7 +927,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
         u32x4 uh, ul;
 #pragma unroll
         for (int ch = 0; ch < 8; ch += 2) {
-            float v0 = xok[e] ? xr[e][ch] * a.in_scale : 0.f, v1 = xok[e] ? xr[e][ch + 1] * a.in_scale : 0.f;
+            // (LEAN: a lane outside the data loaded 0.0f, see LEAN_OOB)
+            float v0 = (LEAN || xok[e]) ? xr[e][ch] * a.in_scale : 0.f, v1 = (LEAN || xok[e]) ? xr[e][ch + 1] * a.in_scale : 0.f;
             v0 = fmaxf(v0, v0 * a.in_slope);
             v1 = fmaxf(v1, v1 * a.in_slope);
             unsigned h, l;
@@ -894,13 +942,18 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
     };
     const half8* xbase = Xp + (unsigned)((half * 2) * SPAN + wn * (NJ * 32) + l31);
     const half8* abase = Aw + (unsigned)(wm * (MI * 128) + lane);
-    auto chunk = [&](int c, auto buf_tag) __attribute__((always_inline)) {
+    // one channel chunk of NTAPS taps (J, or J - 1 in a row tile without the last tap); PAR = weight slot of the chunk's first tap (it flips from
+    // chunk to chunk when NTAPS is odd, as in the wide kernel).  The staging items sit on the last XIT taps that EXIST.
+    auto chunk = [&](int c, auto buf_tag, auto par_tag, auto ntaps_tag) __attribute__((always_inline)) {
         constexpr int BUF = decltype(buf_tag)::value;
+        constexpr int PAR = decltype(par_tag)::value;
+        constexpr int NTAPS = decltype(ntaps_tag)::value;
+        static_assert(XIT <= NTAPS, "one staging item per tap");
         half8* nxt = Xp + (1 - BUF) * BUFSZ;
 #pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int slot = j & 1;   // (J is even: every chunk starts on slot 0)
-            if (j + 1 < J)
+        for (int j = 0; j < NTAPS; ++j) {
+            const int slot = (PAR + j) & 1;
+            if (j + 1 < NTAPS)
                 stage_A(c, j + 1, slot ^ 1);
             else
                 stage_A(c + 1 < NCHUNK ? c + 1 : c, 0, slot ^ 1);
@@ -916,7 +969,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
                 bh[n] = xbase[BUF * BUFSZ + (J - 1 - j) + n * 32];
                 bl[n] = xbase[BUF * BUFSZ + SPAN + (J - 1 - j) + n * 32];
             }
-            const int e = J - 1 - j;
+            const int e = NTAPS - 1 - j;
             if (e < XIT) {
                 x_commit_item(e, nxt);
                 x_issue_item(e, c + 2 < NCHUNK ? c + 2 : NCHUNK - 1);
@@ -945,9 +998,16 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
 #pragma unroll
     for (int e = 0; e < XIT; ++e) x_issue_item(e, 1);
     __syncthreads();
-    for (int c = 0; c < NCHUNK; c += 2) {
-        chunk(c, std::integral_constant<int, 0>());
-        chunk(c + 1, std::integral_constant<int, 1>());
+    if (LEAN && by >= a.short_from) {   // (workgroup-uniform: the row tile is one phase, and that phase has J - 1 real taps)
+        for (int c = 0; c < NCHUNK; c += 2) {
+            chunk(c, std::integral_constant<int, 0>(), std::integral_constant<int, 0>(), std::integral_constant<int, J - 1>());
+            chunk(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, ((J - 1) & 1)>(), std::integral_constant<int, J - 1>());
+        }
+    } else {
+        for (int c = 0; c < NCHUNK; c += 2) {
+            chunk(c, std::integral_constant<int, 0>(), std::integral_constant<int, 0>(), std::integral_constant<int, J>());
+            chunk(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, (J & 1)>(), std::integral_constant<int, J>());
+        }
     }
     // epilogue: virtual row tile -> (phase r, real channel tile); output position o = q * stride + r - padding
     const int q_hi = a.q_lo + a.q_cnt;
@@ -966,8 +1026,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
     }
 }
 
-template <int CIN, int J, int MI, int NJ>
-static int launch_f16_tall(const ConvArgs& a0, int B, hipStream_t s) {
+template <int CIN, int J, int MI, int NJ, bool LEAN>
+static int launch_f16_tall_l(const ConvArgs& a0, int B, hipStream_t s) {
     constexpr int NT = 2 * NJ * 32, SPAN = NT + (J - 1), MT = 2 * MI * 32;
     ConvArgs a = a0;
     dim3 grid((unsigned)ceil_div(a.q_cnt, NT), (unsigned)(a.CoutP / MT), (unsigned)B);
@@ -980,14 +1040,19 @@ static int launch_f16_tall(const ConvArgs& a0, int B, hipStream_t s) {
         grid = dim3(tiles * grid.y, 1, 1);
     }
     constexpr size_t lds = (size_t)2 * (4 * SPAN + 2) * 16 + (size_t)2 * (2 * MI * 2 * 64) * 16;
-    if (int rc = ensure_full_lds((const void*)conv_f16x3_tall_kernel<CIN, J, MI, NJ>)) return rc;
-    hipLaunchKernelGGL((conv_f16x3_tall_kernel<CIN, J, MI, NJ>), grid, dim3(256), lds, s, a);
+    if (int rc = ensure_full_lds((const void*)conv_f16x3_tall_kernel<CIN, J, MI, NJ, LEAN>)) return rc;
+    hipLaunchKernelGGL((conv_f16x3_tall_kernel<CIN, J, MI, NJ, LEAN>), grid, dim3(256), lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("conv_f16x3_tall_kernel launch failed: %s", hipGetErrorString(e));
         return TTSC_EHIP;
     }
     return TTSC_OK;
+}
+
+template <int CIN, int J, int MI, int NJ>
+static int launch_f16_tall(const ConvArgs& a, int B, hipStream_t s) {
+    return a.lean ? launch_f16_tall_l<CIN, J, MI, NJ, true>(a, B, s) : launch_f16_tall_l<CIN, J, MI, NJ, false>(a, B, s);
 }
 
 template <int C, int K>
@@ -1549,6 +1614,8 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
         a.acc_init = 0;
         a.epi_prefetch = 0;
         a.swz_nx = a.swz_ny = 0;
+        a.lean = 0;
+        a.short_from = INT_MAX;
         a.fold_S = a.fold_B = 0;
         a.amax_x = a.amax_w = nullptr;
         a.amax_out = nullptr;
@@ -1664,6 +1731,14 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
             const bool tall0 = g.in_channels == 512 && ph.ntaps == 4 && c->CoutP % 256 == 0;    // ups.0: 256-row tiles
             const bool tall1 = g.in_channels == 256 && ph.ntaps == 6 && c->CoutP % 128 == 0;    // ups.1: 128-row tiles
             const bool tall_shape = tall_on && c->vfused && a.vphase > 0 && !a.gate && c->CinP == g.in_channels && (tall0 || tall1);
+            // lean staging and zero-tap skipping of the wide and tall kernels (see LEAN_OOB): TTSC_CONV_LEAN=0 launches the kernels as they were.  Read
+            // at every launch, like TTSC_CONV_WIDE, so that one process can compare the two.  The buffer path needs 32-bit byte offsets into one
+            // utterance's input with room for the out-of-range marker, and an in_scale for which 0 * in_scale is +0.
+            const char* lean_ev = getenv("TTSC_CONV_LEAN");
+            a.lean = (!(lean_ev && atoi(lean_ev) == 0) && (int64_t)g.in_channels * Lin * 4 < (1ll << 31) && a.in_scale > 0.f && std::isfinite(a.in_scale)) ? 1 : 0;
+            // tall kernel: a row tile that is exactly one phase r lacks the last tap when r + (J - 1) * stride >= kernel_size; a tile that spans
+            // phases keeps all J taps
+            if (tall_shape && (tall0 ? 256 : 128) == g.out_channels) a.short_from = g.kernel_size - (ph.ntaps - 1) * g.stride;
             if (tall_shape && (wide_env == 2 || (long)ceil_div(a.q_cnt, tall0 ? 128 : 256) * (c->CoutP / (tall0 ? 256 : 128)) * B >= want16)) {
                 rc = tall0 ? launch_f16_tall<512, 4, 4, 2>(a, B, s) : launch_f16_tall<256, 6, 2, 4>(a, B, s);
             } else if (wide_env && wide_shape && (wide_env == 2 || (long)ceil_div(a.Lout, 256) * (g.out_channels / 128) * B >= want16)) {

@@ -62,6 +62,11 @@ struct ConvArgs {
     int epi_prefetch; // wide kernel: residual / running-sum operands of the epilogue fetched several tiles ahead (same arithmetic as epilogue_tile)
     int swz_nx, swz_ny;   // tall kernel, XCD-aware 1-D launch (swz_nx > 0): workgroup id -> (q tile, row tile, utterance) such that the row tiles (= the
                           // phases of a transposed convolution) of one q tile run on ONE XCD, back to back: see conv_f16x3_tall_kernel
+    int lean;         // wide / tall kernels: launch the LEAN instantiation (staging loads through a buffer descriptor, zero taps skipped); decided per
+                      // launch by the host (TTSC_CONV_LEAN, Cin * Lin * 4 < 2^31, finite positive in_scale), 0 = the kernels as they were
+    int short_from;   // tall kernel, lean launches: row tiles (= phases of the transposed convolution) at or beyond this index lack the last of the
+                      // `ntaps` taps (kernel tap r + (ntaps-1)*stride >= kernel_size: the packers store zero weights there) and skip it.  Computed by
+                      // the host from kernel_size, stride and the row-tile height, never from weights; INT_MAX when a row tile spans several phases
     int skew;         // wide kernel: start delay of the second resident workgroup per CU, in units of ~4 us (0 = off)
     int dbg;          // ablation switches, ONLY in -DTTSC_ABLATE builds (tools/ablate.cpp; never in libttscube_hip.so): see TTSC_DBG
 #ifdef TTSC_ABLATE
