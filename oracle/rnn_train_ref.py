@@ -4,7 +4,9 @@ backward through time, for tests only.
 torch.nn.GRU (gate order r, z, n):   r = s(xr + W_hr h + b_hr),  z = s(xz + W_hz h + b_hz),  hn = W_hn h + b_hn,
                                      n = tanh(xn + r * hn),      h' = (1 - z) * n + z * h        with xg = W_ih x + b_ih
 torch.nn.LSTM (gate order i, f, g, o): gates = xg + W_hh h,  i, f, o = s(.), g = tanh(.),  c' = f c + i g,  h' = o tanh(c')
-                                     with xg = W_ih x + b_ih + b_hh; the reverse direction walks the steps from T-1 down to 0.
+                                     with xg = W_ih x + b_ih + b_hh; the reverse direction walks the steps from T-1 down to 0
+                                     (from len_b - 1 with ragged `lengths`: lstm_layer_forward, also the inference oracle of
+                                     ttsc_lstm_seq_forward with initial and final states).
 
 Every function takes `dtype`: float64 is the reference, float32 of the same code is the yardstick (what plain fp32 arithmetic makes of
 the same problem).  The outputs are the quantities the kernels save or produce:
@@ -144,28 +146,56 @@ def gru_layer_grads(x, w_ih, w_hh, b_ih, b_hh, dy, h0=None, dtype=np.float64, wi
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- LSTM
-def lstm_layer_forward(xg, whh, dtype=np.float64):
+def _lstm_cell(x, h, c, whhT, H, chain):
+    """one step: x [n,4H] (the xg rows), state h, c [n,H] -> post-activation gates [n,4H], c', h'"""
+    pre = _chain(x, h, whhT) if chain else x + h @ whhT
+    i, f, g, o = _sig(pre[:, :H]), _sig(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), _sig(pre[:, 3 * H:])
+    c = f * c + i * g
+    h = o * np.tanh(c)
+    return np.concatenate([i, f, g, o], axis=1), c, h
+
+
+def lstm_layer_forward(xg, whh, dtype=np.float64, lengths=None, h0=None, c0=None, return_state=False, chain=False):
     """xg [B,T,ndir*4H] (W_ih x + b_ih + b_hh), whh [ndir,4H,H] -> y [B,T,ndir*H], gates [B,T,ndir*4H] (post-activation i,f,g,o),
-    c [B,T,ndir*H]; zero initial state"""
-    xg, whh = _a(xg, dtype), _a(whh, dtype)
+    c [B,T,ndir*H]; with return_state also h_n, c_n [ndir,B,H].  h0 / c0 [ndir,B,H]: the initial state (None: zeros).
+    lengths [B] (None: all T): pack_padded_sequence semantics — direction 1 of utterance b walks len_b - 1 .. 0, y / gates / c are zero at
+    t >= len_b and never read there (those xg rows may hold anything), the final state is the state after the utterance's own last step; a
+    length of 0 gives an all-zero row with h_n = h0, c_n = c0.  chain=True: the W_hh h product is one k-ordered sum starting from the xg
+    value (`_chain`), the summation order of lstm_seq_kernel."""
+    whh = _a(whh, dtype)
     B, T, _ = xg.shape
     nd, H4, H = whh.shape
-    y = np.empty((B, T, nd * H), dtype=dtype)
-    gates = np.empty((B, T, nd * H4), dtype=dtype)
-    cs = np.empty((B, T, nd * H), dtype=dtype)
+    lens = None if lengths is None else np.asarray(lengths).astype(np.int64)
+    if lens is None:
+        xg = _a(xg, dtype)
+    alloc = np.empty if lens is None else np.zeros
+    y = alloc((B, T, nd * H), dtype=dtype)
+    gates = alloc((B, T, nd * H4), dtype=dtype)
+    cs = alloc((B, T, nd * H), dtype=dtype)
+    h_n = np.empty((nd, B, H), dtype=dtype)
+    c_n = np.empty((nd, B, H), dtype=dtype)
     for d in range(nd):
         whhT = np.ascontiguousarray(whh[d].T)
-        h = np.zeros((B, H), dtype=dtype)
-        c = np.zeros((B, H), dtype=dtype)
-        for t in (range(T) if d == 0 else reversed(range(T))):
-            pre = xg[:, t, d * H4:(d + 1) * H4] + h @ whhT
-            i, f, g, o = _sig(pre[:, :H]), _sig(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), _sig(pre[:, 3 * H:])
-            c = f * c + i * g
-            h = o * np.tanh(c)
-            y[:, t, d * H:(d + 1) * H] = h
-            cs[:, t, d * H:(d + 1) * H] = c
-            gates[:, t, d * H4:(d + 1) * H4] = np.concatenate([i, f, g, o], axis=1)
-    return y, gates, cs
+        h = np.zeros((B, H), dtype=dtype) if h0 is None else _a(h0[d], dtype).copy()
+        c = np.zeros((B, H), dtype=dtype) if c0 is None else _a(c0[d], dtype).copy()
+        if lens is None:
+            for t in (range(T) if d == 0 else reversed(range(T))):
+                gt, c, h = _lstm_cell(xg[:, t, d * H4:(d + 1) * H4], h, c, whhT, H, chain)
+                y[:, t, d * H:(d + 1) * H] = h
+                cs[:, t, d * H:(d + 1) * H] = c
+                gates[:, t, d * H4:(d + 1) * H4] = gt
+        else:
+            assert lens.shape == (B,) and lens.min(initial=0) >= 0 and lens.max(initial=0) <= T
+            for s in range(int(lens.max(initial=0))):
+                a = np.nonzero(lens > s)[0]   # the utterances still running; only their own rows of xg are read
+                t = np.full(a.shape, s) if d == 0 else lens[a] - 1 - s
+                gt, ca, ha = _lstm_cell(_a(xg[a, t, d * H4:(d + 1) * H4], dtype), h[a], c[a], whhT, H, chain)
+                h[a], c[a] = ha, ca
+                y[a, t, d * H:(d + 1) * H] = ha
+                cs[a, t, d * H:(d + 1) * H] = ca
+                gates[a, t, d * H4:(d + 1) * H4] = gt
+        h_n[d], c_n[d] = h, c
+    return (y, gates, cs, h_n, c_n) if return_state else (y, gates, cs)
 
 
 def lstm_layer_backward(dy, gates, cs, whh, dtype=np.float64):

@@ -115,6 +115,87 @@ def test_lstm_oracle_gates_cells_and_gate_gradients():
     assert _rel(dG, xg.grad.numpy()) < TOL
 
 
+def _lstm_old_forward(xg, whh):
+    """lstm_layer_forward as it stood before it took lengths / states (zero state, full length), kept here to pin the defaults bit for bit"""
+    B, T, _ = xg.shape
+    nd, H4, H = whh.shape
+    y, gates, cs = np.empty((B, T, nd * H)), np.empty((B, T, nd * H4)), np.empty((B, T, nd * H))
+    for d in range(nd):
+        whhT = np.ascontiguousarray(whh[d].T)
+        h, c = np.zeros((B, H)), np.zeros((B, H))
+        for t in (range(T) if d == 0 else reversed(range(T))):
+            pre = xg[:, t, d * H4:(d + 1) * H4] + h @ whhT
+            i, f, g, o = R._sig(pre[:, :H]), R._sig(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), R._sig(pre[:, 3 * H:])
+            c = f * c + i * g
+            h = o * np.tanh(c)
+            y[:, t, d * H:(d + 1) * H], cs[:, t, d * H:(d + 1) * H] = h, c
+            gates[:, t, d * H4:(d + 1) * H4] = np.concatenate([i, f, g, o], axis=1)
+    return y, gates, cs
+
+
+def test_lstm_oracle_defaults_are_unchanged():
+    rng = np.random.default_rng(4)
+    B, T, H, nd = 3, 11, 12, 2
+    xg, whh = rng.standard_normal((B, T, nd * 4 * H)), 0.3 * rng.standard_normal((nd, 4 * H, H))
+    want = _lstm_old_forward(xg, whh)
+    got = R.lstm_layer_forward(xg, whh)
+    assert len(got) == 3 and all(np.array_equal(a, b) for a, b in zip(got, want))
+    z = np.zeros((nd, B, H))
+    full = R.lstm_layer_forward(xg, whh, lengths=[T] * B, h0=z, c0=z, return_state=True)   # the ragged walk at full length: the same recurrence
+    assert all(_rel(a, b) < TOL for a, b in zip(full[:3], want))
+    assert _rel(full[3][0], want[0][:, -1, :H]) < TOL and _rel(full[3][1], want[0][:, 0, H:]) < TOL
+    assert _rel(full[4][0], want[2][:, -1, :H]) < TOL and _rel(full[4][1], want[2][:, 0, H:]) < TOL
+
+
+@pytest.mark.parametrize('chain', [False, True])
+@pytest.mark.parametrize('bi', [False, True])
+@pytest.mark.parametrize('lens', [[9, 1, 4, 9, 7], [1, 6], [5]])
+def test_lstm_oracle_ragged_with_states_matches_torch_float64(lens, bi, chain):
+    """lengths (including 1 and T), non-zero hx, final states: against torch.nn.LSTM in float64 on a packed batch"""
+    torch.manual_seed(len(lens) * 10 + bi)
+    B, T, I, H, nd = len(lens), max(lens), 5, 8, 2 if bi else 1
+    m = torch.nn.LSTM(I, H, bidirectional=bi, batch_first=True).double()
+    x = torch.randn(B, T, I, dtype=torch.float64)
+    h0 = 0.7 * torch.randn(nd, B, H, dtype=torch.float64)
+    c0 = 1.2 * torch.randn(nd, B, H, dtype=torch.float64)
+    with torch.no_grad():
+        packed = torch.nn.utils.rnn.pack_padded_sequence(x, lens, batch_first=True, enforce_sorted=False)
+        out, (hn, cn) = m(packed, (h0, c0))
+        y, _ = torch.nn.utils.rnn.pad_packed_sequence(out, batch_first=True, total_length=T)
+    p = {k: v.detach().numpy() for k, v in m.named_parameters()}
+    sfx = ['', '_reverse'][:nd]
+    wih = np.concatenate([p['weight_ih_l0' + s] for s in sfx])
+    bias = np.concatenate([p['bias_ih_l0' + s] + p['bias_hh_l0' + s] for s in sfx])
+    whh = np.stack([p['weight_hh_l0' + s] for s in sfx])
+    xg = x.numpy() @ wih.T + bias
+    for b, n in enumerate(lens):
+        xg[b, n:] = np.nan                     # rows beyond the length are never read
+    yo, gates, cs, ho, co = R.lstm_layer_forward(xg, whh, lengths=lens, h0=h0.numpy(), c0=c0.numpy(), return_state=True, chain=chain)
+    assert ho.shape == (nd, B, H) and co.shape == (nd, B, H)
+    assert _rel(yo, y.numpy()) < TOL and _rel(ho, hn.numpy()) < TOL and _rel(co, cn.numpy()) < TOL
+    for b, n in enumerate(lens):
+        assert not yo[b, n:].any() and not gates[b, n:].any() and not cs[b, n:].any()
+        assert np.isfinite(gates[b, :n]).all() and np.isfinite(cs[b, :n]).all()
+
+
+@pytest.mark.parametrize('nd', [1, 2])
+def test_lstm_oracle_zero_length_row(nd):
+    """torch refuses a length of 0: the row is all zeros, its final state is its initial state, the other rows do not notice"""
+    rng = np.random.default_rng(nd)
+    B, T, H = 4, 6, 8
+    lens = [6, 0, 1, 3]
+    xg, whh = rng.standard_normal((B, T, nd * 4 * H)), 0.3 * rng.standard_normal((nd, 4 * H, H))
+    h0, c0 = 0.5 * rng.standard_normal((nd, B, H)), rng.standard_normal((nd, B, H))
+    xg[1] = np.nan
+    y, gates, cs, hn, cn = R.lstm_layer_forward(xg, whh, lengths=lens, h0=h0, c0=c0, return_state=True)
+    assert not y[1].any() and not gates[1].any() and not cs[1].any()
+    assert np.array_equal(hn[:, 1], h0[:, 1]) and np.array_equal(cn[:, 1], c0[:, 1])
+    keep = [0, 2, 3]
+    o = R.lstm_layer_forward(xg[keep], whh, lengths=[lens[b] for b in keep], h0=h0[:, keep], c0=c0[:, keep], return_state=True)
+    for a, b in zip((y[keep], gates[keep], cs[keep], hn[:, keep], cn[:, keep]), o):
+        assert np.isfinite(b).all() and _rel(a, b) < TOL
+
+
 def test_chain_summation_order_is_the_same_recurrence():
     """chain=True only changes the order of the W_hh sums: the same answer in float64"""
     rng = np.random.default_rng(1)
