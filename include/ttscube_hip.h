@@ -826,6 +826,25 @@ int ttsc_pitch_track(const float* cand_lag_dev, const float* cand_val_dev, const
                      const int32_t* nframes_dev, int32_t B, int64_t Fmax, int32_t kmax, float sample_rate, void* workspace_dev, size_t workspace_bytes,
                      float* f0_dev, void* stream);
 
+/* Dynamic time warping of the dev-set evaluation (csrc/dtw.hip; io_utils/evaluate.py; the float64 and float32 statements are
+ * tests/dtw_reference.py): P ragged pairs of feature sequences aligned in one launch, one workgroup per pair.
+ *   a [P, Na_max, K], b [P, Nb_max, K] float32, contiguous; len_a, len_b [P] int32 ON THE DEVICE (clamped to [0, Na_max] / [0, Nb_max]); 1 <= K <= 80.
+ *   d(i, j) = sqrt(sum_k (a[i,k] - b[j,k])^2) from the differences, float32, ascending k, every operation rounded on its own;
+ *   D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)) from (0, 0) to (len_a - 1, len_b - 1), steps unweighted; ties go to the diagonal,
+ *   then to (i-1, j), then to (i, j-1) (strict <, taken in that order).
+ *   cost [P] float32 = D at the end cell; plen [P] int32; path_a, path_b [P, Na_max + Nb_max - 1] int32 in forward order, -1 behind plen.  A pair
+ *   with len_a == 0 or len_b == 0 gets plen 0, cost 0 and paths of -1.  Rows at or beyond a pair's own lengths are never read: a pair's bits do
+ *   not depend on the batch around it.
+ * The local costs are formed inside the launch (no Na x Nb matrix reaches memory), the back-pointers go to the workspace
+ * (ttsc_dtw_workspace_bytes(P, Na_max, Nb_max) bytes, 16-byte aligned: one byte per cell of 64-column blocks, the boundary column between blocks
+ * and the reversed path) and are walked back in the same launch; all index arithmetic is 64-bit and nothing synchronises with the host.
+ * Checked before the launch (nonzero status, the last-error text set): P < 0, K outside 1 .. 80, negative or >= 2^30 lengths, a NULL pointer with
+ * a nonzero size, a workspace that is too small or misaligned.  P == 0 launches nothing. */
+size_t ttsc_dtw_workspace_bytes(int32_t P, int64_t Na_max, int64_t Nb_max);
+int ttsc_dtw_align(const float* a_dev, const float* b_dev, const int32_t* len_a_dev, const int32_t* len_b_dev, int32_t P, int64_t Na_max,
+                   int64_t Nb_max, int32_t K, void* workspace_dev, size_t workspace_bytes, float* cost_dev, int32_t* plen_dev, int32_t* path_a_dev,
+                   int32_t* path_b_dev, void* stream);
+
 /* Rational-rate polyphase FIR resampler of the audio readers (csrc/resample.hip; io_utils/resample.py; the float64 statement is
  * tests/resample_reference.py): scipy.signal.resample_poly(x, up, down) with its default Kaiser-5 filter, for a ragged batch in one launch.
  *   x [B, Lmax] float32, len [B] (clamped to [0, Lmax]); up, down coprime, both in [1, 1024]; half = 10 max(up, down), K = ceil((2 half + 1) / up).

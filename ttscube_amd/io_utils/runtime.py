@@ -13,7 +13,49 @@ from .audio import save_wav
 from .io_cubegan import CubeganCollate, CubeganDataset
 
 
-def cubegan_synthesize_dataset(model, output_path, devset_path, limit=-1, free=True, conditioning=None, speaker=None, word_vectors=None):
+def cubegan_synthesize_batches(model, devset_path, limit=-1, free=True, conditioning=None, speaker=None, word_vectors=None, batch=1):
+    """The synthesis behind cubegan_synthesize_dataset(batch > 1) and io_utils/evaluate.py: yields (ids, (wav [B, L] float32 in (-1, 1) ON THE DEVICE,
+    sample counts)) for `batch` dev items at a time, collated and run through the ragged path of TTSCube.synthesize_batch
+    (Cubegan.inference(return_lengths=True): each row equals its single-item call).  Forced alignment (free=False) has no ragged path: one item
+    per yield."""
+    collate = CubeganCollate(model._encodings, conditioning_type=conditioning, word_vectors=word_vectors)
+    dataset = CubeganDataset(devset_path)
+    m_gen = len(dataset) if limit == -1 or limit >= len(dataset) else limit
+    step = max(int(batch), 1) if free else 1
+    with torch.no_grad():
+        for s in range(0, m_gen, step):
+            exs = [dataset[ii] for ii in range(s, min(s + step, m_gen))]
+            if speaker is not None:
+                for ex in exs:
+                    ex['meta']['speaker'] = speaker
+            X = collate.collate_fn(exs)
+            for key in X:
+                if isinstance(X[key], torch.Tensor):
+                    X[key] = X[key].to(model.get_device())
+            if len(exs) == 1:
+                wav = (model.inference(X) if free else model(X)).detach().reshape(1, -1)
+                lens = [int(wav.shape[1])]
+            else:
+                wav, lens = model.inference(X, return_lengths=True)
+                wav = wav.detach()[:, 0]
+            yield [ex['meta']['id'] for ex in exs], (wav, lens)
+
+
+def cubegan_synthesize_dataset(model, output_path, devset_path, limit=-1, free=True, conditioning=None, speaker=None, word_vectors=None, batch=1):
+    """batch (an addition): 1 = the reference's item-by-item loop; above 1, `batch` items are collated at a time and run as one ragged call
+    (free=True only), each file equal to what the loop writes."""
+    if batch > 1:
+        if not free:
+            raise ValueError('cubegan_synthesize_dataset: batch > 1 runs the ragged inference path and needs free=True')
+        os.makedirs(output_path, exist_ok=True)
+        m_gen = 0
+        for ids, (wav, lens) in cubegan_synthesize_batches(model, devset_path, limit=limit, free=True, conditioning=conditioning, speaker=speaker,
+                                                           word_vectors=word_vectors, batch=batch):
+            wav = wav.cpu().numpy()
+            for j, i in enumerate(ids):
+                save_wav('{0}/{1}.wav'.format(output_path, i), np.asarray(wav[j, :lens[j]] * 32767, dtype=np.int16), 24000)
+            m_gen += len(ids)
+        return m_gen
     collate = CubeganCollate(model._encodings, conditioning_type=conditioning, word_vectors=word_vectors)
     dataset = CubeganDataset(devset_path)
     m_gen = len(dataset) if limit == -1 or limit >= len(dataset) else limit
