@@ -845,6 +845,45 @@ int ttsc_dtw_align(const float* a_dev, const float* b_dev, const int32_t* len_a_
                    int64_t Nb_max, int32_t K, void* workspace_dev, size_t workspace_bytes, float* cost_dev, int32_t* plen_dev, int32_t* path_a_dev,
                    int32_t* path_b_dev, void* stream);
 
+/* Forced aligner (csrc/forced_align.hip; io_utils/forced_align.py; the float32 and float64 statements are tests/forced_align_reference.py): a
+ * time-synchronous Viterbi search of a ragged batch of utterances through left-to-right lattices of diagonal-Gaussian states, and the statistics
+ * of its alignments for Viterbi re-estimation.  Limits, from the 42 KiB of LDS of the search (8 frames x 1024 positions of emissions, two rows of
+ * scores, 8 feature rows): Smax <= 1024 positions per utterance, D <= 63 feature dimensions.
+ *   viterbi   feat [B, Tmax, D] float32, nframes [B] int32 (clamped to [0, Tmax]); the lattice of utterance b: state [B, Smax] int32 (model-state
+ *             id per position), skip [B, Smax] int32 (one extra predecessor < j, or -1), start / final [B, Smax] uint8 flags, npos [B] int32
+ *             (clamped to [0, Smax]); the model: mean, ivar [M, D], cst [M] float32.  All ON THE DEVICE.  In float32, every operation rounded on
+ *             its own: acc = 0; for ascending d: diff = x[d] - mean[m][d], acc = acc + (diff * diff) * ivar[m][d]; e = cst[m] - 0.5f * acc;
+ *             v_0[j] = start[j] ? e_0[j] : -inf; v_t[j] = e_t[j] + best of v_{t-1}[j], v_{t-1}[j-1], v_{t-1}[skip[j]], taken in that order with
+ *             strict > (ties stay on the earlier candidate); the end is the final position with the largest v_{T-1}, ties to the lowest index.
+ *             align [B, Tmax] int32 = position per frame, -1 behind nframes; score [B] float32; ok [B] int32.  An utterance with nframes == 0,
+ *             npos == 0 or no finite path (fewer frames than mandatory positions) gets ok 0, score 0 and -1 throughout.  Nothing at or beyond
+ *             an utterance's own nframes / npos is read: its bits do not depend on the batch around it.  The back-pointers go to the workspace
+ *             (ttsc_fa_workspace_bytes(B, Tmax, Smax) bytes, 16-byte aligned: one byte per cell, 64-bit index arithmetic) and are walked back
+ *             in the same launch; nothing synchronises with the host.
+ *             Checked before the launch (nonzero status, the last-error text set): negative sizes, Tmax >= 2^30, Smax > 1024, D outside 1 .. 63,
+ *             a NULL pointer with a nonzero size, a workspace that is too small or misaligned.  B == 0 launches nothing.
+ *   check_lattice   the lattice tables live on the device, where a launch cannot be refused over their contents without a synchronisation; this
+ *             entry point takes their HOST copies before they are uploaded (the Python wrapper always calls it) and refuses npos outside
+ *             0 .. Smax, a state id outside 0 .. M - 1, a skip that is neither -1 nor an earlier position, and flags other than 0 / 1.  Inside
+ *             the kernel a position with a state id outside the model is closed (-inf) and a skip outside -1 .. j - 1 is taken as -1, so
+ *             unchecked tables cannot make it read out of bounds either.
+ *   accumulate   adds the statistics of the aligned frames into running float64 tables count [M], sum [M, D], sumsq [M, D]: per (utterance,
+ *             position) the sums of x and x * x over the frames with align == position in ascending t (x widened to double first, x * x taken in
+ *             double); per model state those segment sums (segments without a frame left out) are added in ascending (b, position); that batch
+ *             total is added ONCE to the running table.  Utterances with ok == 0 contribute nothing.  No atomics; the result does not depend on
+ *             the launch geometry.  workspace: ttsc_fa_accumulate_workspace_bytes(B, Smax, D) bytes, 16-byte aligned (the segment sums). */
+size_t ttsc_fa_workspace_bytes(int32_t B, int64_t Tmax, int32_t Smax);
+int ttsc_fa_check_lattice(const int32_t* state, const int32_t* skip, const uint8_t* start, const uint8_t* final_, const int32_t* npos, int32_t B,
+                          int32_t Smax, int32_t M);
+int ttsc_fa_viterbi(const float* feat_dev, const int32_t* nframes_dev, const int32_t* state_dev, const int32_t* skip_dev, const uint8_t* start_dev,
+                    const uint8_t* final_dev, const int32_t* npos_dev, const float* mean_dev, const float* ivar_dev, const float* cst_dev, int32_t B,
+                    int64_t Tmax, int32_t Smax, int32_t D, int32_t M, void* workspace_dev, size_t workspace_bytes, int32_t* align_dev,
+                    float* score_dev, int32_t* ok_dev, void* stream);
+size_t ttsc_fa_accumulate_workspace_bytes(int32_t B, int32_t Smax, int32_t D);
+int ttsc_fa_accumulate(const float* feat_dev, const int32_t* nframes_dev, const int32_t* align_dev, const int32_t* ok_dev, const int32_t* state_dev,
+                       const int32_t* npos_dev, int32_t B, int64_t Tmax, int32_t Smax, int32_t D, int32_t M, void* workspace_dev,
+                       size_t workspace_bytes, double* count_dev, double* sum_dev, double* sumsq_dev, void* stream);
+
 /* Rational-rate polyphase FIR resampler of the audio readers (csrc/resample.hip; io_utils/resample.py; the float64 statement is
  * tests/resample_reference.py): scipy.signal.resample_poly(x, up, down) with its default Kaiser-5 filter, for a ragged batch in one launch.
  *   x [B, Lmax] float32, len [B] (clamped to [0, Lmax]); up, down coprime, both in [1, 1024]; half = 10 max(up, down), K = ceil((2 half + 1) / up).

@@ -265,6 +265,11 @@ SIGNATURES = {
     'ttsc_pitch_track': (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     'ttsc_dtw_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
     'ttsc_dtw_align': (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    'ttsc_fa_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
+    'ttsc_fa_check_lattice': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3),
+    'ttsc_fa_viterbi': (C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4),
+    'ttsc_fa_accumulate_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'ttsc_fa_accumulate': (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4),
     'ttsc_resample_poly': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p]),
     'ttsc_story_mix': (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

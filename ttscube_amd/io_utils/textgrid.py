@@ -1,5 +1,5 @@
-"""Reader for Praat TextGrid files as Montreal Forced Aligner writes them: the long ("ooTextFile") and the short text format, interval tiers
-only.  It offers what the reference's importer uses of the `textgrid` package (scripts/import_textgrid.py:249-271): `TextGrid.fromFile(path)`,
+"""Reader and writer for Praat TextGrid files as Montreal Forced Aligner writes them: the long ("ooTextFile") and the short text format are
+read, the long one is written (io_utils/forced_align.py), interval tiers only.  It offers what the reference's importer uses of the `textgrid` package (scripts/import_textgrid.py:249-271): `TextGrid.fromFile(path)`,
 `tg[tier][i].mark / .minTime / .maxTime` and `len(tg[tier])`; a tier is addressed by position or by name.
 
 Both formats carry the same values in the same order; the long one only labels them (`xmin = 0`, `intervals [3]:`).  The reader therefore takes
@@ -117,3 +117,21 @@ class TextGrid:
                 items.append(Interval(a, b, v.string('an interval text')))
             tg.tiers.append(IntervalTier(name, lo, hi, items))
         return tg
+
+    def toString(self):
+        """the long text format; numbers are written with repr, so that fromString returns the same floats"""
+        q = lambda text: '"' + str(text).replace('"', '""') + '"'
+        out = ['File type = "ooTextFile"', 'Object class = "TextGrid"', '', 'xmin = %r' % float(self.minTime), 'xmax = %r' % float(self.maxTime),
+               'tiers? <exists>', 'size = %d' % len(self.tiers), 'item []:']
+        for k, tier in enumerate(self.tiers):
+            out += ['    item [%d]:' % (k + 1), '        class = "IntervalTier"', '        name = %s' % q(tier.name),
+                    '        xmin = %r' % float(tier.minTime), '        xmax = %r' % float(tier.maxTime),
+                    '        intervals: size = %d' % len(tier.intervals)]
+            for i, iv in enumerate(tier.intervals):
+                out += ['        intervals [%d]:' % (i + 1), '            xmin = %r' % float(iv.minTime), '            xmax = %r' % float(iv.maxTime),
+                        '            text = %s' % q(iv.mark)]
+        return '\n'.join(out) + '\n'
+
+    def write(self, path):
+        with open(path, 'w', encoding='utf-8', newline='\n') as f:
+            f.write(self.toString())
