@@ -945,6 +945,24 @@ int ttsc_stft_project(const float* sig_dev, int64_t Lpad, const float* mag_dev, 
 int ttsc_stft_overlap_add(const float* frames_in_dev, const int32_t* frames_host, const int32_t* frames_dev, int32_t B, int32_t Fmax,
                           int32_t n_fft, int32_t hop, const float* tables_dev, int32_t padded, float* out_dev, int64_t ldo, void* stream);
 
+/* Segment feed of the HiFi-GAN trainer (csrc/segment_feed.hip; io_utils/segment_feed.py; the numpy restatement is
+ * tests/segment_feed_reference.py): a batch of B crops of `frames` frames (frames * hop samples) from a device-resident corpus in one launch.
+ * Row b is utterance u = utt[b] from frame s = start_frame[b]:
+ *     y_out[b, 0, i]   = float(wav[wav_off[u] + s hop + i]) * gain[u]              0 at and beyond wav_off[u + 1]
+ *     mel_out[b, c, t] = mel[(mel_off[u] + s + t) n_mels + c] * mel_scale          mel_pad where s + t >= mel_off[u + 1] - mel_off[u]
+ * one float32 product per element; no sums, no atomics: a row has the same bits alone and in any batch.
+ *   wav_arena  int16 samples of all U utterances, wav_off [U + 1] int64 (the 16-byte load path needs wav_off[u] + s hop on a multiple of 8 and an
+ *              arena base aligned to 16 bytes; anything else takes the 2-byte path, same bits); gain [U] float32
+ *   mel_arena  float32 [sum F_u, n_mels], frame-major, mel_off [U + 1] int64 in FRAMES; NULL: audio only (mel_off, mel_out are then ignored)
+ *   utt, start_frame  [B] int32 ON THE DEVICE: 0 <= utt[b] < U, start_frame[b] >= 0 — the caller's promise (io_utils/segment_feed.py checks its
+ *              host copies); a start beyond an utterance's end gives zeros / mel_pad and reads nothing
+ *   y_out [B, 1, frames hop], mel_out [B, n_mels, frames] (channel-major: what Generator takes)
+ * Checked here: 1 <= B <= 65535, frames, hop >= 1, frames hop < 2^31, 1 <= n_mels <= 255 with a mel arena, NULL pointers, alignment to the
+ * element type.  All arena indexing is 64-bit. */
+int ttsc_segment_gather(const int16_t* wav_arena_dev, const int64_t* wav_off_dev, const float* gain_dev, const float* mel_arena_dev,
+                        const int64_t* mel_off_dev, const int32_t* utt_dev, const int32_t* start_frame_dev, int32_t B, int32_t n_mels,
+                        int32_t frames, int32_t hop, float mel_scale, float mel_pad, float* y_out_dev, float* mel_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -279,6 +279,7 @@ SIGNATURES = {
     'ttsc_stft_synthesize': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
     'ttsc_stft_project': (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
     'ttsc_stft_overlap_add': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'ttsc_segment_gather': (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_float, C.c_float] + [C.c_void_p] * 3),
 }
 
 
