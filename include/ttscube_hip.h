@@ -106,7 +106,12 @@ int ttsc_conv1d_forward(const ttsc_conv1d* c, const float* x_dev, int32_t B, int
                         const float* resid_dev, const ttsc_conv1d_epilogue* ep, void* stream);
 /* ragged batch: in_len_dev / out_len_dev int32 [B] (device) give each utterance's valid input / output length inside
  * the padded [B,C,L] tensors; input beyond in_len[b] reads as zero (== the utterance run alone), tiles wholly beyond
- * out_len[b] are skipped (their output is unspecified).  NULL = dense. */
+ * out_len[b] are skipped (their output is unspecified).  NULL = dense.
+ * What the kernels do with the tail today (held by tests/test_conv_infer_f64_gpu.py and tests/test_conv1d_gpu.py): the column tile that
+ * holds an utterance's last valid position is stored whole — its positions at or beyond out_len[b] receive the layer's result on the
+ * zero-extended input, the bits of the dense call — and skipped tiles keep what the buffer held.  The tile is the launch's: 128 .. 512
+ * columns in the general kernels, 256 in the wide kernel, 1024 in the Cout = 1 kernel.  The ResBlock chain kernels (ttsc_rbchain_forward)
+ * store nothing at or beyond an utterance's length. */
 int ttsc_conv1d_forward_ragged(const ttsc_conv1d* c, const float* x_dev, int32_t B, int64_t Lin, float* y_dev,
                                const float* resid_dev, const ttsc_conv1d_epilogue* ep, const int32_t* in_len_dev,
                                const int32_t* out_len_dev, void* stream);

@@ -256,6 +256,7 @@ def test_fused_resblock_chain_matches_torch(C, k, dils, L, B, shape):
         solo = _chain_ref(x[:1, :, :n], ws, k)
         assert float((y[:1, :, :n].cpu() - solo).abs().max()) < 3e-5
         assert float((y[1:].cpu() - ref[1:]).abs().max()) < 3e-5
+        assert bool((y[:1, :, n:] == 7.0).all())          # the chain kernels store nothing at or beyond an utterance's own length
 
 
 def test_interleaved_chain_is_bit_identical_to_the_plain_layout(monkeypatch):
@@ -322,7 +323,7 @@ def test_conv1d_f16x3_wide_tile_kernel(C, k, d, L, B, monkeypatch):
         from ttscube_amd import _lib
         n = L - 77
         lens = torch.tensor([n] + [L] * (B - 1), dtype=torch.int32).cuda()
-        yr = torch.zeros(B, C, L, device='cuda')
+        yr = torch.full((B, C, L), 7.0, device='cuda')
         ep = _lib.Conv1dEpilogue(1.0, 0.1, 1.0, _lib.ACT_NONE, 0, None, 1.0)
         xd = x.cuda()
         _lib.check(_lib.lib().ttsc_conv1d_forward_ragged(conv._h, _lib.dev_ptr(xd), B, L, _lib.dev_ptr(yr), None, C_.byref(ep),
@@ -330,6 +331,14 @@ def test_conv1d_f16x3_wide_tile_kernel(C, k, d, L, B, monkeypatch):
         solo = conv(x[:1, :, :n].contiguous().cuda(), in_slope=0.1)
         assert torch.equal(yr[:1, :, :n], solo)           # ragged == the utterance run alone, bit for bit
         assert torch.equal(yr[1:], y[1:])
+        # the tail: the 256-column tile that holds the utterance's last position is stored whole, computed from input read as zero beyond the
+        # length (= the dense call on the zero-extended utterance); tiles wholly beyond the length are skipped and keep what the buffer held
+        xz = x[:1].clone()
+        xz[:, :, n:] = 0
+        yz = conv(xz.cuda(), in_slope=0.1)
+        end = min(L, (n + 255) // 256 * 256)
+        assert torch.equal(yr[:1, :, n:end], yz[:, :, n:end])
+        assert bool((yr[:1, :, end:] == 7.0).all())
 
 
 @pytest.mark.parametrize('cin,k,L,B,prec', [(32, 7, 5003, 2, 'f16x3'), (32, 7, 1024, 1, 'fp32'), (64, 11, 2050, 1, 'f16x3'), (20, 3, 7, 2, 'fp32')])

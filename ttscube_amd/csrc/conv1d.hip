@@ -1100,6 +1100,20 @@ static int launch_cfg(const ConvArgs& a, int B, hipStream_t s) {
     return TTSC_OK;
 }
 
+// TTSC_CONV_TILE=<rows>x<cols> forces the tile of the general split kernel and of the fp32 kernel (tests: every tile variant at small shapes).
+// Read at every launch, like TTSC_CONV_WIDE.  0 = unset, 1 = parsed, -1 = malformed.  A tile the layer cannot take is an error at the launch,
+// never another tile: the error is what proves which variant ran.
+static int forced_tile(int* rows, int* cols) {
+    const char* ev = getenv("TTSC_CONV_TILE");
+    if (!ev || !*ev) return 0;
+    int r = 0, c = 0;
+    char x = 0, tail = 0;
+    if (sscanf(ev, "%d%c%d%c", &r, &x, &c, &tail) != 3 || (x != 'x' && x != 'X') || r <= 0 || c <= 0) return -1;
+    *rows = r;
+    *cols = c;
+    return 1;
+}
+
 static int pick_mt(int Cout) {
     int best = 32, best_pad = (int)round_up(Cout, 32);
     for (int mt : {64, 128}) {
@@ -1681,6 +1695,10 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
         a.gate = ep ? ep->gate_dev : nullptr;
         a.gate_slope = ep ? ep->gate_slope : 1.f;
         int rc;
+        int ft_rows = 0, ft_cols = 0;
+        const int ft_rc = forced_tile(&ft_rows, &ft_cols);
+        TTSC_REQUIRE(ft_rc >= 0, "ttsc_conv1d_forward: TTSC_CONV_TILE must be <rows>x<cols>, e.g. 64x256 (got '%s')", getenv("TTSC_CONV_TILE"));
+        const bool ft_set = ft_rc > 0;
         if (use_cout1) {
             // one output channel (conv_post): vector-ALU kernel, bound by the single read of its input
             a.wp = w_plain;
@@ -1746,6 +1764,27 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
                     rc = launch_f16_wide_k<256>(a, B, g.dilation, s);
                 else
                     rc = launch_f16_wide_k<128>(a, B, g.dilation, s);
+            } else if (ft_set) {
+                // forced tile: one of the three the fill rule below could pick for this MT class, through the same span bookkeeping
+                const bool m64 = c->MT >= 64;
+                if (m64 && ft_rows == 64 && ft_cols == 256) {
+                    rc = launch_f16<2, 2>(a, B, s);
+                } else if (m64 && ft_rows == 64 && ft_cols == 128) {
+                    set_nt16(128);
+                    rc = launch_f16<2, 1>(a, B, s);
+                } else if (!m64 && ft_rows == 32 && ft_cols == 512) {
+                    rc = launch_f16<1, 4>(a, B, s);
+                } else if (!m64 && ft_rows == 32 && ft_cols == 256) {
+                    set_nt16(256);
+                    rc = launch_f16<1, 2>(a, B, s);
+                } else if (ft_rows == 32 && ft_cols == 128) {
+                    set_nt16(128);
+                    rc = launch_f16<1, 1>(a, B, s);
+                } else {
+                    set_error("ttsc_conv1d_forward: TTSC_CONV_TILE=%dx%d is not a split-kernel tile of this layer (MT %d: %s, 32x128)", ft_rows, ft_cols,
+                              c->MT, m64 ? "64x256, 64x128" : "32x512, 32x256");
+                    return TTSC_EINVAL;
+                }
             } else if (c->MT >= 64) {
                 if (big_only || wgs16(64, 256) >= want16)
                     rc = launch_f16<2, 2>(a, B, s);   // 64 x 256 tile (MT=128 layers run as two M tiles)
@@ -1783,7 +1822,22 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
             // cuts the padded columns by more than an eighth (this kernel is bound by its MFMA count, not by operand reuse)
             auto padded = [&](int nt) { return (long)ceil_div(a.q_cnt, nt) * nt; };
             auto narrower_pays = [&](int nt_big, int nt_small) { return narrow_env && padded(nt_small) * 8 < padded(nt_big) * 7; };
-            if (c->MT == 128) {
+            if (ft_set) {
+                // forced tile: one of the three the fill rule below could pick for this MT class
+                const int mt = c->MT, r = ft_rows, n = ft_cols;
+                if (mt == 128 && r == 128 && n == 128) { set_nt(128); rc = launch_cfg<2, 2, 2, 2>(a, B, s); }
+                else if (mt >= 64 && r == 64 && n == 128) { set_nt(128); rc = launch_cfg<1, 2, 2, 2>(a, B, s); }
+                else if (mt >= 64 && r == 64 && n == 64) { set_nt(64); rc = launch_cfg<1, 1, 2, 2>(a, B, s); }
+                else if (mt == 64 && r == 64 && n == 256) { set_nt(256); rc = launch_cfg<2, 2, 1, 4>(a, B, s); }
+                else if (mt == 32 && r == 32 && n == 512) { set_nt(512); rc = launch_cfg<1, 4, 1, 4>(a, B, s); }
+                else if (mt == 32 && r == 32 && n == 256) { set_nt(256); rc = launch_cfg<1, 2, 1, 4>(a, B, s); }
+                else if (mt == 32 && r == 32 && n == 128) { set_nt(128); rc = launch_cfg<1, 1, 1, 4>(a, B, s); }
+                else {
+                    set_error("ttsc_conv1d_forward: TTSC_CONV_TILE=%dx%d is not an fp32 tile of this layer (MT %d: %s)", r, n, mt,
+                              mt == 128 ? "128x128, 64x128, 64x64" : (mt == 64 ? "64x256, 64x128, 64x64" : "32x512, 32x256, 32x128"));
+                    return TTSC_EINVAL;
+                }
+            } else if (c->MT == 128) {
                 if (wgs(128, 128) >= want && !narrower_pays(128, 64)) { set_nt(128); rc = launch_cfg<2, 2, 2, 2>(a, B, s); }
                 else if (wgs(64, 128) >= want && !narrower_pays(128, 64)) { set_nt(128); rc = launch_cfg<1, 2, 2, 2>(a, B, s); }
                 else { set_nt(64); rc = launch_cfg<1, 1, 2, 2>(a, B, s); }
