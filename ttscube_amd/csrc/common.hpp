@@ -36,6 +36,13 @@ int device_cus();
 // Raises hipFuncAttributeMaxDynamicSharedMemorySize of `fn` on the CURRENT device to the full 160 KiB once per (device, function).
 // Kernels that declare more than 64 KiB of dynamic LDS call this before every launch (a map lookup under a mutex).
 int ensure_full_lds(const void* fn);
+// After a kernel launch: TTSC_OK, or the launch error recorded as "<kernel> launch failed: ..." and TTSC_EHIP.
+inline int launch_checked(const char* kernel) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return TTSC_OK;
+    set_error("%s launch failed: %s", kernel, hipGetErrorString(e));
+    return TTSC_EHIP;
+}
 // Hand-off area of a split recurrence: `nwords` counters, the launch's abort word (both re-zeroed on the stream before every
 // launch: an aborted launch cannot poison the next one) and a STICKY copy of the abort that survives until handoff_status()
 // has reported it, plus an optional exchange buffer.  One area per (device, stream, tag): two handles driven on two streams of one device — or on two devices of

@@ -1,13 +1,13 @@
 // Device code shared by the convolution translation units (conv1d.hip: inference and exact-fp32 training launches; conv_train.hip:
 // split-precision training launches): launch arguments, the fused epilogues, the exact-fp32 implicit-GEMM kernel and the general
-// split-precision kernel.
+// split-precision kernel.  The wide / tall split-precision kernels live in conv_f16x3_widetall.hpp, the pieces all three share in
+// conv_f16x3_tile.hpp.
 #pragma once
 #include "common.hpp"
+#include "conv_f16x3_tile.hpp"
 #include "conv_internal.hpp"
 
 namespace ttsc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Ablation switches exist only in the measurement build (-DTTSC_ABLATE, tools/ablate.cpp); the product library compiles
 // them to constants, so no environment variable can make a shipped kernel skip work.
@@ -67,7 +67,6 @@ struct ConvArgs {
     int short_from;   // tall kernel, lean launches: row tiles (= phases of the transposed convolution) at or beyond this index lack the last of the
                       // `ntaps` taps (kernel tap r + (ntaps-1)*stride >= kernel_size: the packers store zero weights there) and skip it.  Computed by
                       // the host from kernel_size, stride and the row-tile height, never from weights; INT_MAX when a row tile spans several phases
-    int skew;         // wide kernel: start delay of the second resident workgroup per CU, in units of ~4 us (0 = off)
     int dbg;          // ablation switches, ONLY in -DTTSC_ABLATE builds (tools/ablate.cpp; never in libttscube_hip.so): see TTSC_DBG
 #ifdef TTSC_ABLATE
     unsigned long long* prof;   // workgroup phase timeline (TTSC_STAMP) or null; env TTSC_PROF_PTR
@@ -408,8 +407,6 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_mfma_kernel(ConvArgs a) {
 // ONCE per workgroup through LDS (double-buffered, prefetched one tap ahead) instead of once per wave from L2.
 // Activation tile: LDS [position][16 channels] fp16 (hi and lo planes), so a B fragment (8 consecutive channels of
 // one position) is a single 16-byte ds_read; the fp32 -> (hi,lo) split and the leaky-relu prologue happen while staging.
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 template <int MI, int NJ, int TMAX, bool FOLD = false>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -440,10 +437,10 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs a) {
     bool acc_init = false;
     if constexpr (!FOLD) acc_init = a.acc_init != 0;
     if (acc_init) {
-        // The square layers of the wide stages start their sums at (residual + running sum + bias) / w_unscale — conv_f16x3_wide_kernel's
-        // arithmetic (conv1d.hip), operation for operation, so that a layer gives the same bits whichever of the two kernels the machine-fill rule
-        // picks (a short utterance run alone takes this kernel, the same utterance inside a large batch the wide one).  Host guarantees: plain
-        // stride-1 convolution, no activation, no gate, out_scale == 1, B * Cout * Lout < 2^32.
+        // The square layers of the wide stages start their sums at (residual + running sum + bias) / w_unscale: the acc_init_add / acc_init_scale steps
+        // conv_f16x3_wide_kernel calls too, so that a layer gives the same bits whichever of the two kernels the machine-fill rule picks (a short
+        // utterance run alone takes this kernel, the same utterance inside a large batch the wide one).  Host guarantees: plain stride-1
+        // convolution, no activation, no gate, out_scale == 1, B * Cout * Lout < 2^32.
         const float inv = 1.f / a.w_unscale;
         const float* first = a.resid ? a.resid : (a.accumulate ? a.y : nullptr);
         const float* second = (a.resid && a.accumulate) ? a.y : nullptr;
@@ -469,11 +466,13 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs a) {
                     for (int r = 0; r < 16; ++r) acc[i][n][r] = first[o + (unsigned)((r & 3) + 8 * (r >> 2)) * L1];
                 }
                 if (second) {
+                    float sv[16];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][n][r] += second[o + (unsigned)((r & 3) + 8 * (r >> 2)) * L1];
+                    for (int r = 0; r < 16; ++r) sv[r] = second[o + (unsigned)((r & 3) + 8 * (r >> 2)) * L1];
+                    acc_init_add(acc[i][n], sv);
                 }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][n][r] = (acc[i][n][r] + bv[r]) * inv;
+                acc_init_add(acc[i][n], bv);
+                acc_init_scale(acc[i][n], inv);
             }
         }
     } else {
@@ -561,22 +560,9 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs a) {
         for (int e = 0; e < XIT; ++e) {
             if (xslot[e] >= 0) {
                 const int cb = c * 16 + xh[e] * 8;
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                u32x4 uh, ul;
-#pragma unroll
-                for (int ch = 0; ch < 8; ch += 2) {
-                    float v0 = (xok[e] && cb + ch < cin_n) ? xr[e][ch] * in_scale : 0.f;
-                    float v1 = (xok[e] && cb + ch + 1 < cin_n) ? xr[e][ch + 1] * in_scale : 0.f;
-                    v0 = fmaxf(v0, v0 * a.in_slope);   // leaky-relu for slopes in [0,1] (1 = identity)
-                    v1 = fmaxf(v1, v1 * a.in_slope);
-                    unsigned h, l;
-                    split2_f16(v0, v1, h, l);   // (conv_internal.hpp: packed hi / lo split, same bits as the scalar sequence)
-                    uh[ch >> 1] = h;
-                    ul[ch >> 1] = l;
-                }
-                const half8 vh = __builtin_bit_cast(half8, uh), vl = __builtin_bit_cast(half8, ul);
-                Xp[xslot[e]] = vh;
-                Xp[xslot[e] + a.span_pad] = vl;
+                const half8x2 v = lrelu_split8(xr[e], in_scale, a.in_slope, [&](int ch) { return xok[e] && cb + ch < cin_n; });
+                Xp[xslot[e]] = v.hi;
+                Xp[xslot[e] + a.span_pad] = v.lo;
             }
         }
     };
@@ -615,19 +601,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs a) {
                 bh[n] = xh[shift + n * 32];
                 bl[n] = xl[shift + n * 32];
             }
-            // three product terms; consecutive MFMAs go to DIFFERENT accumulators (no back-to-back dependency)
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int n = 0; n < NJ; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[n], acc[i][n], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int n = 0; n < NJ; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[n], acc[i][n], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int n = 0; n < NJ; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[n], acc[i][n], 0, 0, 0);
+            TTSC_MFMA3_F16X3(MI, NJ, acc, ah, al, bh, bl);
         }
     }
 
@@ -650,9 +624,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvArgs a) {
             }
             if (acc_init) {   // everything but the weight scale is in the sum already
                 if (q < q_hi && q < a.Lout) {
-                    float* yp = a.y + ((size_t)b * a.Cout + (cot0 + i) * 32 + 4 * half) * a.Lout + q;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) yp[(size_t)((r & 3) + 8 * (r >> 2)) * a.Lout] = acc[i][n][r] * a.w_unscale;
+                    acc_init_store(acc[i][n], a.w_unscale, a.y + ((size_t)b * a.Cout + (cot0 + i) * 32 + 4 * half) * a.Lout + q, a.Lout);
                 }
                 continue;
             }
