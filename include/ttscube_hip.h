@@ -463,6 +463,26 @@ int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel_dev, const float* xlow
                         int32_t mode, const float* noise_dev, uint64_t seed, const float* forced_x_dev,
                         uint8_t* idx_dev, float* wav_dev, float* logits_dev, void* workspace_dev, size_t workspace_bytes,
                         void* stream);
+/* Ragged decode: per-row lengths in both decode kernels.  Arguments of ttsc_wavernn_decode plus four HOST tables, which are
+ * copied (one stream synchronisation, as in ttsc_hifigan_forward_ragged):
+ *   frames_host  int32 [B]   valid mel frames of row b, 1..T
+ *   low_len_host int32 [B]   valid x_low samples of row b, 1..Tl (hr net); NULL for the low-resolution net
+ *   seed_host    uint64 [B]  Philox key of row b, or NULL: every row uses `seed`
+ *   stream_host  uint32 [B]  what stands in Philox counter word 2 in place of the row's batch position, or NULL: the row index
+ * Row b emits L_b = min(frames[b]*upsample, low_len[b]*upsample_low) samples (frames[b]*upsample for the low-resolution net).  T,
+ * Tl and L = out_len(T, Tl) stay the row strides of every [B, ...] buffer (noise, forced_x and logits included).  For t < L_b, idx /
+ * wav / logits of row b are bit for bit what ttsc_wavernn_decode gives for that row's valid prefix alone, called with
+ * T = frames[b], Tl = low_len[b], seed = seed[b] and the row at batch position stream[b]: the k = 7 convolutions' zero padding and
+ * the interpolation's end clamp sit at the row's own low_len.  Nothing is stored at t >= L_b, and no input element beyond a row's
+ * own lengths influences any output (the padding may hold anything, NaN included).  A length of 0 or above T / Tl, or a missing
+ * low_len_host for the hr net, is TTSC_EINVAL before any launch.  Kernel choice and ttsc_wavernn_last_status are those of
+ * ttsc_wavernn_decode; a tile of the tile kernel runs as many steps as the longest of ITS eight rows, a workgroup of the
+ * streaming kernel as many as the longest of its rows. */
+int ttsc_wavernn_decode_ragged(ttsc_wavernn* w, const float* mel_dev, const float* xlow_dev, int32_t B, int64_t T, int64_t Tl,
+                               const int32_t* frames_host, const int32_t* low_len_host, const uint64_t* seed_host,
+                               const uint32_t* stream_host, int32_t mode, const float* noise_dev, uint64_t seed,
+                               const float* forced_x_dev, uint8_t* idx_dev, float* wav_dev, float* logits_dev, void* workspace_dev,
+                               size_t workspace_bytes, void* stream);
 /* Which kernel ran the last decode and whether its hand-offs completed.  Synchronises `stream`, then: -1 = single-workgroup
  * streaming kernel; 2 = tile kernel (8 workgroups step 8 utterances, each owning an eighth of the weight rows; chosen for
  * one-layer networks (any output head) when ceil(B/8)*8 <= number of CUs, H <= 512; env TTSC_WR_TILE=0 turns it off);

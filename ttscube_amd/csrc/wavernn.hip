@@ -17,9 +17,14 @@
 //   * pre-output (tanh Linear H->256), output (Linear 256->S), Gumbel-max sampling, µ-law decode and the
 //     feedback of the sample all stay inside the workgroup (LDS + 3 barriers).
 //
+// Ragged batches (ttsc_wavernn_decode_ragged): the same kernels with RAG = true.  Row b emits row_L[b] samples; a workgroup loops to the
+// longest of its rows, a finished row keeps being stepped with its stores suppressed, and Philox is keyed by the row's own seed with the
+// row's own stream in counter word 2 — a row's bits are those of its valid prefix decoded alone, wherever it sits in the batch.
+//
 // Arithmetic contract = oracle/wavernn_ref.c: every dot product is one k-ordered fp32 fmaf chain seeded with the
 // bias, transcendental functions from include/ttscube_math.h, compiled with -ffp-contract=off.  That makes the
 // uint8 sample indices bit-exact against the oracle (tests/test_wavernn_gpu.py).
+#include <algorithm>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -54,28 +59,36 @@ struct WrArgs {
     int B, T, Tl, H, NL, use_lowres, up, up_low, S, n_mel, out_kind, mode;
     int L;
     unsigned long long seed;
+    // ragged launches (wr_decode_kernel<BT, true>): per-row tables, [B] each; null otherwise
+    const int* row_L;                    // samples row b emits (<= L); nothing is stored at t >= row_L[b]
+    const unsigned* row_stream;          // Philox counter word 2 of row b (in place of its batch position)
+    const unsigned long long* row_seed;  // Philox key of row b
 };
 
 // ---- conditioning: linear interpolation x10 and the three tanh(Conv1d k7) low-res layers --------------------
 // (modules.py:353,416-420,458-461).  One workgroup per utterance; chain order = (ci outer, k inner), bias seed.
 __global__ __launch_bounds__(256) void wr_cond_kernel(const float* __restrict__ x_low, const float* w0, const float* b0,
                                                       const float* w1, const float* b1, const float* w2, const float* b2,
-                                                      float* interp, float* fa, float* fb, int Tl, int up_low) {
+                                                      float* interp, float* fa, float* fb, int Tl, int up_low, const int* low_len) {
+    // Tl is the row stride of every buffer; Tv the row's own length (ragged launches): the interpolation's end clamp and the
+    // convolutions' zero padding sit at Tv, exactly where they sit when the row's valid prefix is decoded alone.  Nothing at or
+    // beyond Tv is read, and nothing there is written.
     const int b = blockIdx.x;
+    const int Tv = low_len ? low_len[b] : Tl;
     const float* x = x_low + (size_t)b * Tl;
-    const int n = Tl * up_low;
-    const float scale = (float)Tl / (float)n;
+    const int n = Tv * up_low;
+    const float scale = (float)Tv / (float)n;
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
         float src = scale * ((float)t + 0.5f) - 0.5f;
         if (src < 0.f) src = 0.f;
         int i0 = (int)src;
-        if (i0 > Tl - 1) i0 = Tl - 1;
-        const int i1 = i0 + (i0 < Tl - 1 ? 1 : 0);
+        if (i0 > Tv - 1) i0 = Tv - 1;
+        const int i1 = i0 + (i0 < Tv - 1 ? 1 : 0);
         const float l1 = src - (float)i0;
         const float l0 = 1.0f - l1;
         const float p0 = l0 * x[i0];
         const float p1 = l1 * x[i1];
-        interp[(size_t)b * n + t] = p0 + p1;
+        interp[(size_t)b * ((size_t)Tl * up_low) + t] = p0 + p1;
     }
     float* A = fa + (size_t)b * 20 * Tl;
     float* Bf = fb + (size_t)b * 20 * Tl;
@@ -85,16 +98,16 @@ __global__ __launch_bounds__(256) void wr_cond_kernel(const float* __restrict__ 
         const float* w = layer == 0 ? w0 : (layer == 1 ? w1 : w2);
         const float* bb = layer == 0 ? b0 : (layer == 1 ? b1 : b2);
         const int cin = layer == 0 ? 1 : 20;
-        for (int idx = threadIdx.x; idx < 20 * Tl; idx += blockDim.x) {
-            const int co = idx / Tl, t = idx - co * Tl;
+        for (int idx = threadIdx.x; idx < 20 * Tv; idx += blockDim.x) {
+            const int co = idx / Tv, t = idx - co * Tv;
             float acc = bb[co];
             for (int ci = 0; ci < cin; ++ci)
                 for (int k = 0; k < 7; ++k) {
                     const int p = t + k - 3;
-                    const float v = (p >= 0 && p < Tl) ? in[ci * Tl + p] : 0.f;
+                    const float v = (p >= 0 && p < Tv) ? in[ci * Tl + p] : 0.f;
                     acc = fmaf(w[(co * cin + ci) * 7 + k], v, acc);
                 }
-            out[idx] = ttsc_tanhf(acc);
+            out[co * Tl + t] = ttsc_tanhf(acc);
         }
         __threadfence_block();
         __syncthreads();
@@ -117,7 +130,10 @@ __device__ __forceinline__ float chain_matvec_quarters(const float* __restrict__
     return tot;
 }
 
-template <int BT>
+// RAG: ragged launch (ttsc_wavernn_decode_ragged).  The workgroup steps until the longest of its BT rows is done; a finished row keeps
+// being stepped (rows never interact) and its stores are suppressed; the Philox key and counter word 2 come from the per-row tables.
+// A template parameter, so that the dense kernel is the code it was.
+template <int BT, bool RAG>
 __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int H = a.H, S = a.S, NL = a.NL, NM = a.n_mel;
@@ -126,6 +142,9 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
     float* score = pre + BT * 256;             // [BT][S]
     float* xin = score + BT * S;               // [BT][128]: mel frame | low-res feats
     float* lastx = xin + BT * 128;             // [BT]
+    int* rowL = reinterpret_cast<int*>(lastx + 16);              // RAG: [BT] samples per row
+    unsigned* rowS = reinterpret_cast<unsigned*>(rowL + 8);      // RAG: [BT] Philox stream
+    unsigned* rowK = rowS + 8;                                   // RAG: [BT][2] Philox key (low, high word)
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int j = tid;                          // hidden unit owned by this thread
@@ -137,6 +156,16 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
     // array: a runtime-indexed register array would be demoted to scratch.
 #define BIDX(u) (min((int)blockIdx.x * BT + (u), a.B - 1))
 #define BOK(u) ((int)blockIdx.x * BT + (u) < a.B)
+#define ROK(u) (BOK(u) && (!RAG || t < rowL[u]))
+#define RSTREAM(u) (RAG ? rowS[u] : (uint32_t)BIDX(u))
+#define RSEED(u) (RAG ? (((unsigned long long)rowK[2 * (u) + 1] << 32) | rowK[2 * (u)]) : a.seed)
+    if (RAG && tid < BT) {
+        rowL[tid] = BOK(tid) ? a.row_L[BIDX(tid)] : 0;
+        rowS[tid] = a.row_stream[BIDX(tid)];
+        const unsigned long long k = a.row_seed[BIDX(tid)];
+        rowK[2 * tid] = (unsigned)k;
+        rowK[2 * tid + 1] = (unsigned)(k >> 32);
+    }
     for (int i = tid; i < 2 * NL * BT * H; i += WR_THREADS) hbuf[i] = 0.f;
     if (tid < BT) lastx[tid] = 0.f;
 
@@ -160,7 +189,13 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
     int cur = 0;
     int fr = 0, fr_phase = 0;  // t / up, t % up   (incremental: no integer division in the step loop)
     int lo = 0, lo_phase = 0;  // t / up_low, t % up_low
-    for (int t = 0; t < a.L; ++t) {
+    int Lwg = a.L;             // steps of this workgroup: the longest of its rows
+    if (RAG) {
+        Lwg = 0;
+#pragma unroll
+        for (int u = 0; u < BT; ++u) Lwg = max(Lwg, rowL[u]);
+    }
+    for (int t = 0; t < Lwg; ++t) {
         // ---- refresh the cached prefixes of the layer-0 input chain --------------------------------------
         const bool new_frame = fr_phase == 0;
         const bool new_low = a.use_lowres && lo_phase == 0;
@@ -276,7 +311,7 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
                 if (row < S) {
                     const float acc = chain_matvec_quarters(a.wt_out, S, row, pre + u * 256, 256, a.b_out[row]);
                     const size_t o = ((size_t)BIDX(u) * a.L + t) * S + row;
-                    if (a.out_logits && BOK(u)) a.out_logits[o] = acc;
+                    if (a.out_logits && ROK(u)) a.out_logits[o] = acc;
                     float g = 0.f;
                     if (a.out_kind >= 2) {
                         // continuous outputs: the noise enters in the sampler stage below
@@ -284,8 +319,8 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
                         g = a.noise[o];
                     } else if (a.mode == 2) {
                         uint32_t r4[4];
-                        ttsc_philox4x32((uint32_t)(row >> 2), (uint32_t)t, (uint32_t)BIDX(u), 0u,
-                                        (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r4);
+                        const unsigned long long key = RSEED(u);
+                        ttsc_philox4x32((uint32_t)(row >> 2), (uint32_t)t, RSTREAM(u), 0u, (uint32_t)key, (uint32_t)(key >> 32), r4);
                         g = ttsc_gumbel(r4[row & 3]);
                     }
                     score[u * S + row] = acc + g;
@@ -302,9 +337,9 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
                 const size_t o = (size_t)BIDX(u) * a.L + t;
                 float wv;
                 int bi;
-                wr_sample_continuous(a.out_kind, a.mode, y, a.noise, o, t, BIDX(u), a.seed, lane, wv, bi);
+                wr_sample_continuous(a.out_kind, a.mode, y, a.noise, o, t, (int)RSTREAM(u), RSEED(u), lane, wv, bi);
                 if (lane == 0) {
-                    if (BOK(u)) {
+                    if (ROK(u)) {
                         a.out_idx[o] = (uint8_t)bi;
                         a.out_wav[o] = wv;
                     }
@@ -339,7 +374,7 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
                 else
                     wv = (((float)bi / 255.0f) - 0.5f) * 2.0f;
                 const size_t o = (size_t)BIDX(u) * a.L + t;
-                if (BOK(u)) {
+                if (ROK(u)) {
                     a.out_idx[o] = (uint8_t)bi;
                     a.out_wav[o] = wv;
                 }
@@ -355,6 +390,9 @@ __global__ __launch_bounds__(WR_THREADS) void wr_decode_kernel(WrArgs a) {
 
 #undef BIDX
 #undef BOK
+#undef ROK
+#undef RSTREAM
+#undef RSEED
 
 }  // namespace ttsc
 
@@ -624,14 +662,25 @@ static size_t cond_bytes(const ttsc_wavernn* w, int32_t B, int64_t Tl) {
     return (size_t)round_up((int64_t)(((size_t)B * Tl * w->cfg.upsample_low + 2 * (size_t)B * 20 * Tl) * sizeof(float)) + 256, 256);
 }
 
+// Per-row tables of a ragged launch, behind the exchange area: low_len | row_L | stream | group_L (int32 each), then the 64-bit keys.
+struct WrRagTab {
+    const int* low_len = nullptr;    // null for the low-resolution net
+    const int* row_L = nullptr;
+    const unsigned* row_stream = nullptr;
+    const int* group_L = nullptr;    // [ceil(B / 8)]: steps of every tile of the tile kernel = the longest of its rows
+    const unsigned long long* row_seed = nullptr;
+};
+static size_t rag_words(int32_t B) { return (size_t)round_up((int64_t)3 * B + ceil_div(B, WT_NC), 2); }
+static size_t rag_bytes(int32_t B) { return (size_t)round_up((int64_t)(rag_words(B) * 4 + (size_t)B * 8), 256); }
+
 extern "C" size_t ttsc_wavernn_workspace_bytes(const ttsc_wavernn* w, int32_t B, int64_t T, int64_t Tl) {
     if (!w) return 0;
-    return cond_bytes(w, B, Tl) + tile_exchange_bytes(w, B);
+    return cond_bytes(w, B, Tl) + tile_exchange_bytes(w, B) + rag_bytes(B);
 }
 
-extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const float* x_low, int32_t B, int64_t T, int64_t Tl,
-                                   int32_t mode, const float* noise, uint64_t seed, const float* forced_x, uint8_t* idx,
-                                   float* wav, float* logits, void* ws, size_t ws_bytes, void* stream) {
+static int wavernn_decode_impl(ttsc_wavernn* w, const float* mel, const float* x_low, int32_t B, int64_t T, int64_t Tl,
+                               int32_t mode, const float* noise, uint64_t seed, const float* forced_x, uint8_t* idx,
+                               float* wav, float* logits, void* ws, size_t ws_bytes, void* stream, const WrRagTab* rag) {
     TTSC_REQUIRE(w && mel && idx && wav, "ttsc_wavernn_decode: null argument");
     TTSC_REQUIRE(B > 0 && T > 0, "ttsc_wavernn_decode: bad B/T");
     TTSC_REQUIRE(mode >= 0 && mode <= 2, "ttsc_wavernn_decode: mode must be 0 (argmax), 1 (injected noise) or 2 (philox)");
@@ -665,7 +714,7 @@ extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const floa
         float* fa = interp + (size_t)B * Tl * c.upsample_low;
         float* fb = fa + (size_t)B * 20 * Tl;
         hipLaunchKernelGGL(wr_cond_kernel, dim3(B), dim3(256), 0, s, x_low, w->lc_w[0], w->lc_b[0], w->lc_w[1], w->lc_b[1],
-                           w->lc_w[2], w->lc_b[2], interp, fa, fb, (int)Tl, c.upsample_low);
+                           w->lc_w[2], w->lc_b[2], interp, fa, fb, (int)Tl, c.upsample_low, rag ? rag->low_len : (const int*)nullptr);
         a.interp = interp;
         a.feats = fa;
     }
@@ -704,6 +753,11 @@ extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const floa
         a.L = (int)L64;
     }
     a.seed = seed;
+    if (rag) {
+        a.row_L = rag->row_L;
+        a.row_stream = rag->row_stream;
+        a.row_seed = rag->row_seed;
+    }
     TTSC_REQUIRE(a.L > 0, "ttsc_wavernn_decode: nothing to decode (L=%d)", a.L);
     if (tile_supported(w, B) && a.L < (1 << 24)) {   // (candidate granules carry a 24-bit step tag)
         const int NC = WT_NC, BU = WT_NC;
@@ -736,15 +790,27 @@ extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const floa
         qa.use_lowres = c.use_lowres; qa.up = c.upsample; qa.up_low = c.upsample_low; qa.S = c.S; qa.SP = (int)round_up(c.S, NC); qa.SR = qa.SP / NC;
         qa.n_mel = c.n_mel; qa.out_kind = c.out_kind; qa.mode = mode; qa.L = a.L; qa.G = G; qa.seed = seed;
         qa.GP = (int)round_up(G, WT_XCDS);
+        if (rag) {
+            qa.row_L = rag->row_L;
+            qa.row_stream = rag->row_stream;
+            qa.row_seed = rag->row_seed;
+            qa.group_L = rag->group_L;
+        }
         // all tags (and the abort word) start at zero; the first step carries tag 1
         TTSC_HIP_CHECK(hipMemsetAsync(xbase, 0, tile_exchange_granules(w, G) * 8 + 64, s));
         const size_t lds = tile_lds_bytes(w);
         if (lds > 64 * 1024) {
             // full 160 KiB once per (device, kernel): a later model with a larger H, or a second device, needs no re-arming
-            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<false, false>)) return rc;
-            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<true, false>)) return rc;
-            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<false, true>)) return rc;
-            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<true, true>)) return rc;
+            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<false, false, false>)) return rc;
+            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<true, false, false>)) return rc;
+            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<false, true, false>)) return rc;
+            if (int rc = ensure_full_lds((const void*)wr_tile_kernel<true, true, false>)) return rc;
+            if (rag) {
+                if (int rc = ensure_full_lds((const void*)wr_tile_kernel<false, false, true>)) return rc;
+                if (int rc = ensure_full_lds((const void*)wr_tile_kernel<true, false, true>)) return rc;
+                if (int rc = ensure_full_lds((const void*)wr_tile_kernel<false, true, true>)) return rc;
+                if (int rc = ensure_full_lds((const void*)wr_tile_kernel<true, true, true>)) return rc;
+            }
         }
 #ifdef TTSC_ABLATE
         unsigned long long* prof_dev = nullptr;
@@ -755,15 +821,26 @@ extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const floa
         }
 #endif
         const dim3 tg(qa.GP * NC), tb(WT_THREADS);
-        if (c.num_layers == 2) {
+        if (rag) {
+            if (c.num_layers == 2) {
+                if (c.out_kind >= 2)
+                    hipLaunchKernelGGL((wr_tile_kernel<true, true, true>), tg, tb, lds, s, qa);
+                else
+                    hipLaunchKernelGGL((wr_tile_kernel<false, true, true>), tg, tb, lds, s, qa);
+            } else if (c.out_kind >= 2) {
+                hipLaunchKernelGGL((wr_tile_kernel<true, false, true>), tg, tb, lds, s, qa);
+            } else {
+                hipLaunchKernelGGL((wr_tile_kernel<false, false, true>), tg, tb, lds, s, qa);
+            }
+        } else if (c.num_layers == 2) {
             if (c.out_kind >= 2)
-                hipLaunchKernelGGL((wr_tile_kernel<true, true>), tg, tb, lds, s, qa);
+                hipLaunchKernelGGL((wr_tile_kernel<true, true, false>), tg, tb, lds, s, qa);
             else
-                hipLaunchKernelGGL((wr_tile_kernel<false, true>), tg, tb, lds, s, qa);
+                hipLaunchKernelGGL((wr_tile_kernel<false, true, false>), tg, tb, lds, s, qa);
         } else if (c.out_kind >= 2) {
-            hipLaunchKernelGGL((wr_tile_kernel<true, false>), tg, tb, lds, s, qa);
+            hipLaunchKernelGGL((wr_tile_kernel<true, false, false>), tg, tb, lds, s, qa);
         } else {
-            hipLaunchKernelGGL((wr_tile_kernel<false, false>), tg, tb, lds, s, qa);
+            hipLaunchKernelGGL((wr_tile_kernel<false, false, false>), tg, tb, lds, s, qa);
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
@@ -812,13 +889,23 @@ extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const floa
         const int v = atoi(ev);
         if (v == 1 || v == 2 || v == 4 || v == 8) bt = v;
     }
-    const size_t lds = ((size_t)2 * c.num_layers * bt * c.H + (size_t)bt * 256 + (size_t)bt * c.S + (size_t)bt * 128 + 16) * sizeof(float);
+    // (+32 words behind the 16 of lastx: the per-row tables of a ragged launch)
+    const size_t lds = ((size_t)2 * c.num_layers * bt * c.H + (size_t)bt * 256 + (size_t)bt * c.S + (size_t)bt * 128 + 16 + (rag ? 32 : 0)) * sizeof(float);
     dim3 grid((unsigned)ceil_div(B, bt));
-    switch (bt) {
-        case 1: hipLaunchKernelGGL(wr_decode_kernel<1>, grid, dim3(WR_THREADS), lds, s, a); break;
-        case 2: hipLaunchKernelGGL(wr_decode_kernel<2>, grid, dim3(WR_THREADS), lds, s, a); break;
-        case 4: hipLaunchKernelGGL(wr_decode_kernel<4>, grid, dim3(WR_THREADS), lds, s, a); break;
-        default: hipLaunchKernelGGL(wr_decode_kernel<8>, grid, dim3(WR_THREADS), lds, s, a); break;
+    if (rag) {
+        switch (bt) {
+            case 1: hipLaunchKernelGGL((wr_decode_kernel<1, true>), grid, dim3(WR_THREADS), lds, s, a); break;
+            case 2: hipLaunchKernelGGL((wr_decode_kernel<2, true>), grid, dim3(WR_THREADS), lds, s, a); break;
+            case 4: hipLaunchKernelGGL((wr_decode_kernel<4, true>), grid, dim3(WR_THREADS), lds, s, a); break;
+            default: hipLaunchKernelGGL((wr_decode_kernel<8, true>), grid, dim3(WR_THREADS), lds, s, a); break;
+        }
+    } else {
+        switch (bt) {
+            case 1: hipLaunchKernelGGL((wr_decode_kernel<1, false>), grid, dim3(WR_THREADS), lds, s, a); break;
+            case 2: hipLaunchKernelGGL((wr_decode_kernel<2, false>), grid, dim3(WR_THREADS), lds, s, a); break;
+            case 4: hipLaunchKernelGGL((wr_decode_kernel<4, false>), grid, dim3(WR_THREADS), lds, s, a); break;
+            default: hipLaunchKernelGGL((wr_decode_kernel<8, false>), grid, dim3(WR_THREADS), lds, s, a); break;
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -826,6 +913,65 @@ extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const floa
         return TTSC_EHIP;
     }
     return TTSC_OK;
+}
+
+extern "C" int ttsc_wavernn_decode(ttsc_wavernn* w, const float* mel, const float* x_low, int32_t B, int64_t T, int64_t Tl,
+                                   int32_t mode, const float* noise, uint64_t seed, const float* forced_x, uint8_t* idx,
+                                   float* wav, float* logits, void* ws, size_t ws_bytes, void* stream) {
+    return wavernn_decode_impl(w, mel, x_low, B, T, Tl, mode, noise, seed, forced_x, idx, wav, logits, ws, ws_bytes, stream, nullptr);
+}
+
+// Ragged decode: row b emits L_b = min(frames[b] * upsample, low_len[b] * upsample_low) samples (frames[b] * upsample for the
+// low-resolution net) — bit for bit what ttsc_wavernn_decode gives for that row's valid prefix alone with T = frames[b],
+// Tl = low_len[b], seed = seed[b] and the row at batch position stream[b].  The four tables are HOST pointers and are copied.
+extern "C" int ttsc_wavernn_decode_ragged(ttsc_wavernn* w, const float* mel, const float* x_low, int32_t B, int64_t T, int64_t Tl,
+                                          const int32_t* frames_host, const int32_t* low_len_host, const uint64_t* seed_host,
+                                          const uint32_t* stream_host, int32_t mode, const float* noise, uint64_t seed,
+                                          const float* forced_x, uint8_t* idx, float* wav, float* logits, void* ws, size_t ws_bytes,
+                                          void* stream) {
+    TTSC_REQUIRE(w && mel && idx && wav, "ttsc_wavernn_decode_ragged: null argument");
+    TTSC_REQUIRE(B > 0 && T > 0, "ttsc_wavernn_decode_ragged: bad B/T");
+    TTSC_REQUIRE(frames_host, "ttsc_wavernn_decode_ragged: frames_host is missing");
+    const auto& c = w->cfg;
+    TTSC_REQUIRE(!c.use_lowres || (low_len_host && Tl > 0), "ttsc_wavernn_decode_ragged: the high-res network needs low_len_host (and x_low)");
+    std::vector<int32_t> tab(rag_words(B) + (size_t)2 * B, 0);
+    int32_t* low_len = tab.data();
+    int32_t* row_L = low_len + B;
+    uint32_t* row_stream = reinterpret_cast<uint32_t*>(row_L + B);
+    int32_t* group_L = row_L + 2 * B;
+    for (int b = 0; b < B; ++b) {
+        TTSC_REQUIRE(frames_host[b] >= 1 && frames_host[b] <= T, "ttsc_wavernn_decode_ragged: frames[%d]=%d outside [1,%lld]", b, frames_host[b],
+                     (long long)T);
+        int64_t Lb = (int64_t)frames_host[b] * c.upsample;
+        if (c.use_lowres) {
+            TTSC_REQUIRE(low_len_host[b] >= 1 && low_len_host[b] <= Tl, "ttsc_wavernn_decode_ragged: low_len[%d]=%d outside [1,%lld]", b,
+                         low_len_host[b], (long long)Tl);
+            low_len[b] = low_len_host[b];
+            Lb = std::min<int64_t>(Lb, (int64_t)low_len_host[b] * c.upsample_low);
+        }
+        TTSC_REQUIRE(Lb < (1ll << 31), "ttsc_wavernn_decode_ragged: more than 2^31 samples per utterance");
+        row_L[b] = (int32_t)Lb;
+        row_stream[b] = stream_host ? stream_host[b] : (uint32_t)b;
+        group_L[b / WT_NC] = std::max(group_L[b / WT_NC], (int32_t)Lb);   // computed from the tile's rows: no order is assumed
+    }
+    uint64_t* row_seed = reinterpret_cast<uint64_t*>(tab.data() + rag_words(B));
+    for (int b = 0; b < B; ++b) row_seed[b] = seed_host ? seed_host[b] : seed;
+    const size_t need = ttsc_wavernn_workspace_bytes(w, B, T, Tl);
+    if (!ws || ws_bytes < need) {
+        set_error("ttsc_wavernn_decode_ragged: workspace %zu < required %zu bytes", ws_bytes, need);
+        return TTSC_ENOMEM;
+    }
+    char* dtab = (char*)ws + cond_bytes(w, B, Tl) + tile_exchange_bytes(w, B);
+    TTSC_HIP_CHECK(hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    TTSC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));   // `tab` is pageable host memory going out of scope
+    WrRagTab rt;
+    const int32_t* d = reinterpret_cast<const int32_t*>(dtab);
+    rt.low_len = c.use_lowres ? d : nullptr;
+    rt.row_L = d + B;
+    rt.row_stream = reinterpret_cast<const unsigned*>(d + 2 * B);
+    rt.group_L = d + 3 * B;
+    rt.row_seed = reinterpret_cast<const unsigned long long*>(d + rag_words(B));
+    return wavernn_decode_impl(w, mel, x_low, B, T, Tl, mode, noise, seed, forced_x, idx, wav, logits, ws, ws_bytes, stream, &rt);
 }
 
 

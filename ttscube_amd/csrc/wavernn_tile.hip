@@ -29,6 +29,9 @@
 // Hand-offs.  Every exchanged value travels as an 8-byte granule {fp32 value, step tag} that the consumer lanes poll: the granule protocol of
 // handoff.hpp, with WT_SPIN_LIMIT and the abort word of this launch only.  No barrier on the consumer side beyond the one that publishes the
 // staged vector in LDS.  Members of a tile are placed on one XCD (blockIdx -> XCD is round-robin).
+//
+// Ragged batches (RAG = true).  The eight members of a tile read ONE step count, group_L[g] = the longest of the tile's rows, before the loop:
+// they run the same number of steps, so the hand-off protocol is exactly the dense one.  A finished row is stepped on, its stores suppressed.
 #include "handoff.hpp"
 #include "rnn_chain.hpp"
 #include "wavernn_sampler.hpp"
@@ -80,6 +83,11 @@ struct WtArgs {
     int B, T, Tl, H, UPW, I0, I0P, use_lowres, up, up_low, S, SP, SR, n_mel, out_kind, mode, L, G, GP, NL;
     unsigned long long seed;
     unsigned long long* prof;   // -DTTSC_ABLATE: [workgroup][16] accumulated 100 MHz ticks per segment (thread 0), or null
+    // ragged launches (RAG instantiations): per-row tables [B] and the per-tile step count [G]; null otherwise
+    const int* row_L;                    // samples row b emits (<= L); nothing is stored at t >= row_L[b]
+    const unsigned* row_stream;          // Philox counter word 2 of row b (in place of its batch position)
+    const unsigned long long* row_seed;  // Philox key of row b
+    const int* group_L;                  // steps of tile g = the longest of its rows: ALL eight members read it here, so they run the same number of steps
 };
 
 // A k-ordered chain block on the 4x4x1 fp32 matrix instruction, NB accumulators (4 utterances each) per lane:
@@ -349,7 +357,11 @@ __device__ __noinline__ void wt_row_block(const glb_float* W_g, const lds_float*
 // second layer.  Per step the second layer adds ONE product to the critical path — W_ih2 . h1_t, which needs this step's h1 —
 // and one hand-off (h2_t); its recurrent product W_hh2 . h2_{t-1} rides with W_hh1 . h1_{t-1} on waves 1..3 behind the tail of
 // the previous step.  All three products stream their member slice from L2 / Infinity Cache (1.18 MB per member and step).
-template <bool CONT, bool L2>
+// RAG: ragged launch (ttsc_wavernn_decode_ragged).  The hand-off protocol is untouched: the eight members of a tile all take their
+// loop bound from group_L[g], so none leaves a hand-off early; a row that has finished keeps being stepped (rows never interact in
+// the arithmetic) and only its stores are suppressed.  The Philox key and counter word 2 come from the per-row tables, read at the
+// head of the tail, where wave 0 waits for the output quarters anyway.  A template parameter: the dense kernels are the code they were.
+template <bool CONT, bool L2, bool RAG>
 __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
     constexpr int NC = WT_NC, BU = WT_NC, PR = 256 / WT_NC;   // PR = 32 pre-output rows per member
     // LDS: wpre[H/4][32][4] | wout[64][32][4] | hvec[BU][VH] | pvec[BU][VP] | gbuf[3*UPW][BU] | bias[32 + 32 + 3*UPW] | tail_fail, pre_ready
@@ -361,6 +373,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
     const int xcd = blockIdx.x % WT_XCDS, slot = blockIdx.x / WT_XCDS;
     const int g = xcd * (a.GP / WT_XCDS) + slot / NC, m = slot % NC;
     if (g >= a.G) return;
+    const int Lg = RAG ? a.group_L[g] : a.L;   // steps of this tile, the same for its eight members
     const int VH = H + 4, VP = 256 + 4;   // +4: the utterances a wave reads per LDS access land in different banks
     float* wpreL = sm;
     float* woutL = wpreL + (size_t)H * PR;
@@ -530,6 +543,8 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
         // While waves 4..7 compute and gather the pre-output vector, this wave draws the step's Gumbel noise for its classes (it depends on
         // (class, step, utterance) only): off the critical path instead of behind the output chain.
         float gn[4] = {0.f, 0.f, 0.f, 0.f};
+        // RAG: does the row of this lane's accumulator column (tutt) still emit at step s?
+        const bool live_t = !RAG || s < a.row_L[min(g * BU + tutt, a.B - 1)];
         if constexpr (!CONT) {
             const int bs = g * BU + tutt, s0 = m * SR + trow;   // s0 is a multiple of 4: one Philox block covers this lane's classes
             if (a.mode == 1 && bs < a.B) {
@@ -538,7 +553,9 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                     if (trow + i < SR && s0 + i < S) gn[i] = a.noise[((size_t)bs * a.L + s) * S + s0 + i];
             } else if (a.mode == 2) {
                 uint32_t r4[4];
-                ttsc_philox4x32((uint32_t)(s0 >> 2), (uint32_t)s, (uint32_t)bs, 0u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r4);
+                const unsigned long long key = RAG ? a.row_seed[min(bs, a.B - 1)] : a.seed;
+                const uint32_t strm = RAG ? a.row_stream[min(bs, a.B - 1)] : (uint32_t)bs;
+                ttsc_philox4x32((uint32_t)(s0 >> 2), (uint32_t)s, strm, 0u, (uint32_t)key, (uint32_t)(key >> 32), r4);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) gn[i] = ttsc_gumbel(r4[i]);
             }
@@ -558,7 +575,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                 const int s_ = m * SR + trow + i;
                 if (trow + i < SR) {
                     if constexpr (CONT) st_granule(xlog + ((size_t)par * BU + tutt) * SP + s_, acc[0][i], tag);
-                    if (a.out_logits && s_ < S && g * BU + tutt < a.B) a.out_logits[((size_t)(g * BU + tutt) * a.L + s) * S + s_] = acc[0][i];
+                    if (a.out_logits && s_ < S && g * BU + tutt < a.B && live_t) a.out_logits[((size_t)(g * BU + tutt) * a.L + s) * S + s_] = acc[0][i];
                 }
             }
             if constexpr (!CONT) {
@@ -602,10 +619,12 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
             float wv;
             int bi;
             const size_t o = (size_t)bs * a.L + s;
-            wr_sample_continuous(a.out_kind, a.mode, ybuf, a.noise, o, s, bs, a.seed, lane, wv, bi);
+            wr_sample_continuous(a.out_kind, a.mode, ybuf, a.noise, o, s, RAG ? (int)a.row_stream[bs] : bs, RAG ? a.row_seed[bs] : a.seed, lane, wv, bi);
             if (lane == 0) {
-                a.out_idx[o] = (uint8_t)bi;
-                a.out_wav[o] = wv;
+                if (!RAG || s < a.row_L[bs]) {
+                    a.out_idx[o] = (uint8_t)bi;
+                    a.out_wav[o] = wv;
+                }
                 st_granule(xlx + par * BU + m, a.forced_x ? a.forced_x[o] : wv, tag);
             }
           }
@@ -633,7 +652,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
                 if (bs < a.B) {
                     const size_t o = (size_t)bs * a.L + s;
                     if (a.forced_x) fed = a.forced_x[o];
-                    if (cu == m) {   // the utterance's own member writes its outputs
+                    if (cu == m && (!RAG || s < a.row_L[bs])) {   // the utterance's own member writes its outputs
                         a.out_idx[o] = (uint8_t)bi;
                         a.out_wav[o] = wv;
                     }
@@ -646,7 +665,7 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
     };
 
     int fr = 0, fr_phase = 0, lo = 0, lo_phase = 0;
-    for (int t = 0; t < a.L; ++t) {
+    for (int t = 0; t < Lg; ++t) {
         const int par = t & 1;
         WT_TICK(0);
         // ---- fork: wave 0 finishes step t-1, waves 1..3 run the recurrent product of step t (both read hvec = h_{t-1}) ----
@@ -794,8 +813,8 @@ __global__ __launch_bounds__(WT_THREADS) void wr_tile_kernel(WtArgs a) {
         if (++fr_phase == a.up) { fr_phase = 0; ++fr; }
         if (++lo_phase == a.up_low) { lo_phase = 0; ++lo; }
     }
-    if (wave >= 4) linears_quarter(a.L - 1);
-    if (wave == 0) tail(a.L - 1);
+    if (wave >= 4) linears_quarter(Lg - 1);
+    if (wave == 0) tail(Lg - 1);
 #ifdef TTSC_ABLATE
     if (a.prof && tid == 0)
         for (int i = 0; i < 8; ++i) a.prof[(size_t)blockIdx.x * 16 + i] = pacc[i];

@@ -97,3 +97,33 @@ class GriffinLimVocoder:
         mag = _stft.mel_to_linear(mel_log10, self.sample_rate, self.num_mels, self.n_fft)
         y = _stft.griffinlim(mag, n_iter=self.n_iter, n_fft=self.n_fft, hop=self.hop_size, rng=np.random.RandomState(self.seed))
         return y.clamp_(-1.0, 1.0).unsqueeze(1)
+
+
+class WaveRNNVocoder:
+    """The `vocoder` contract of io_utils/runtime.py::synthesize_devset for a CubenetVocoder (NOT in the reference, whose WaveRNN path takes one
+    utterance per call): natural-log mel [B, num_mels, F] on the device -> audio [B, 1, L] on the device, L = the longest item's
+    high-resolution length, zeros behind a shorter item.  The items go through ``CubenetVocoder._synthesize_batch_device`` `batch` at a time
+    (both nets as ragged rows); ``frames`` (valid frames per item, default F) keeps padding frames out of the decode.  Item i is seeded with
+    seed + i, so its audio does not depend on `batch`; ``last_lengths`` holds the per-item sample counts of the last call."""
+
+    def __init__(self, vocoder, batch=16, seed=0, mode='philox', num_batches=20):
+        self.vocoder, self.batch, self.seed, self.mode, self.num_batches = vocoder, max(1, int(batch)), seed, mode, num_batches
+        self.last_lengths = []
+
+    def __call__(self, mel, frames=None):
+        mel = torch.as_tensor(mel, dtype=torch.float32)
+        if mel.dim() == 2:
+            mel = mel.unsqueeze(0)
+        B, _, F = mel.shape
+        frames = [F] * B if frames is None else [int(f) for f in frames]
+        mels = [(mel[b, :, :frames[b]].t() * (1.0 / math.log(10.0))).contiguous() for b in range(B)]
+        out = []
+        for k in range(0, B, self.batch):
+            seeds = [self.seed + i for i in range(k, min(k + self.batch, B))]
+            out += [hr for _, hr in self.vocoder._synthesize_batch_device(mels[k:k + self.batch], num_batches=self.num_batches, seed=seeds,
+                                                                           mode=self.mode)]
+        self.last_lengths = [int(o.shape[0]) for o in out]
+        audio = torch.zeros((B, 1, max(self.last_lengths)), dtype=torch.float32, device=out[0].device)
+        for b, o in enumerate(out):
+            audio[b, 0, :o.shape[0]] = o
+        return audio.clamp_(-1.0, 1.0)

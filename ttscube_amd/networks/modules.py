@@ -116,13 +116,20 @@ class WaveRNN(nn.Module):
         except Exception:
             pass
 
-    def decode(self, X, mode='philox', noise=None, seed=None, forced_x=None, want_logits=False):
+    def decode(self, X, mode='philox', noise=None, seed=None, forced_x=None, want_logits=False, lengths=None, low_lengths=None,
+               seeds=None, streams=None):
         """Device-side decode.  Returns (idx uint8 [B,L], wav fp32 [B,L], logits fp32 [B,L,S] | None) as device tensors.
 
         mode: 'philox' (in-kernel counter RNG, seeded from torch's generator unless `seed` is given), 'noise' (injected noise
         [B, L, output_functions.noise_width]: Gumbel terms for mulaw/raw, the sampler's random terms for mol/gm/beta — used by the
         parity tests) or 'argmax' (no noise: the arg-max class / the mode of the selected component).  idx holds the class index
-        (mulaw/raw), the mixture index (mol) or zeros."""
+        (mulaw/raw), the mixture index (mol) or zeros.
+
+        lengths (valid mel frames per row, 1..T) makes the call ragged (``ttsc_wavernn_decode_ragged``): row b emits
+        L_b = min(lengths[b] * upsample, low_lengths[b] * upsample_low) samples, bit for bit those of its valid prefix decoded alone
+        with seed ``seeds[b]`` at batch position ``streams[b]`` (defaults: `seed`, the row index).  The padding beyond a row's lengths
+        may hold anything.  Returns (idx, wav, logits | None, [L_b]) with zeros beyond each row's L_b; noise / forced_x / logits keep
+        the dense indexing [B, L, ...]."""
         L = _lib.lib()
         self._sync()
         dev = self._get_device()
@@ -134,9 +141,13 @@ class WaveRNN(nn.Module):
             Tl = x_low.shape[1]
         Lout = int(L.ttsc_wavernn_out_len(self._handle, T, Tl))
         S = self._output_functions.sample_size
-        idx = torch.empty((B, Lout), dtype=torch.uint8, device=dev)
-        wav = torch.empty((B, Lout), dtype=torch.float32, device=dev)
-        logits = torch.empty((B, Lout, S), dtype=torch.float32, device=dev) if want_logits else None
+        ragged = lengths is not None
+        if not ragged and (low_lengths is not None or seeds is not None or streams is not None):
+            raise _lib.TTSCError('WaveRNN.decode: low_lengths / seeds / streams belong to a ragged call (give lengths)')
+        alloc = torch.zeros if ragged else torch.empty   # nothing is stored beyond a row's L_b: hand out zeros there
+        idx = alloc((B, Lout), dtype=torch.uint8, device=dev)
+        wav = alloc((B, Lout), dtype=torch.float32, device=dev)
+        logits = alloc((B, Lout, S), dtype=torch.float32, device=dev) if want_logits else None
         m = {'argmax': _lib.WR_MODE_ARGMAX, 'noise': _lib.WR_MODE_NOISE, 'philox': _lib.WR_MODE_PHILOX}[mode]
         nz = None
         if mode == 'noise':
@@ -157,16 +168,38 @@ class WaveRNN(nn.Module):
         if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != mel.device:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
         P = _lib.dev_ptr
+        if ragged:
+            def table(v, name, ctype):
+                if v is None:
+                    return None
+                v = [int(x) for x in (v.tolist() if hasattr(v, 'tolist') else v)]
+                if len(v) != B:
+                    raise _lib.TTSCError('WaveRNN.decode: %s has %d entries for a batch of %d' % (name, len(v), B))
+                return (ctype * B)(*v)
+            fr = table(lengths, 'lengths', C.c_int32)
+            ll = table(low_lengths, 'low_lengths', C.c_int32)
+            sd = table(seeds, 'seeds', C.c_uint64)
+            sm = table(streams, 'streams', C.c_uint32)
         with _lib.on_device(mel.device):
-            _lib.check(L.ttsc_wavernn_decode(self._handle, P(mel), P(x_low) if x_low is not None else None, B, T, Tl, m,
-                                             P(nz) if nz is not None else None, C.c_uint64(seed),
-                                             P(fx) if fx is not None else None, P(idx), P(wav),
-                                             P(logits) if logits is not None else None, P(self._ws), self._ws.numel() * 4,
-                                             _lib.current_stream()), 'ttsc_wavernn_decode')
+            if ragged:
+                _lib.check(L.ttsc_wavernn_decode_ragged(self._handle, P(mel), P(x_low) if x_low is not None else None, B, T, Tl, fr, ll,
+                                                        sd, sm, m, P(nz) if nz is not None else None, C.c_uint64(seed),
+                                                        P(fx) if fx is not None else None, P(idx), P(wav),
+                                                        P(logits) if logits is not None else None, P(self._ws),
+                                                        self._ws.numel() * 4, _lib.current_stream()), 'ttsc_wavernn_decode_ragged')
+            else:
+                _lib.check(L.ttsc_wavernn_decode(self._handle, P(mel), P(x_low) if x_low is not None else None, B, T, Tl, m,
+                                                 P(nz) if nz is not None else None, C.c_uint64(seed),
+                                                 P(fx) if fx is not None else None, P(idx), P(wav),
+                                                 P(logits) if logits is not None else None, P(self._ws), self._ws.numel() * 4,
+                                                 _lib.current_stream()), 'ttsc_wavernn_decode')
             st = L.ttsc_wavernn_last_status(self._handle, _lib.current_stream())
             if st == 1:
                 raise _lib.TTSCError('WaveRNN multi-workgroup kernel aborted on a hand-off timeout: ' + L.ttsc_last_error().decode())
             self.last_kernel = {2: 'tile'}.get(st, 'stream')
+        if ragged:
+            up, ul = self._upsample, self._upsample_low
+            return idx, wav, logits, [min(fr[b] * up, ll[b] * ul) if self._use_lowres else fr[b] * up for b in range(B)]
         return idx, wav, logits
 
     def forward(self, X):

@@ -70,6 +70,64 @@ class CubenetVocoder(nn.Module):
         xl[1:, 0:self._upsample_low] = x_low_split[:-1, -self._upsample_low:]
         return {'mel': m, 'x_low': xl}
 
+    # ---- a LIST of utterances through both nets as ragged rows (not in the reference, which synthesizes one utterance per call) ----
+    def _synthesize_batch_device(self, mels, num_batches=20, max_rows=None, seed=None, mode='philox'):
+        """mels: list of [T_i, 80] log10-mels.  Returns a list of (x_lr [24 T_i], x_hr) DEVICE tensors in input order; item i has the
+        bits of ``_inference({'mel': mels[i][None]}, seed=s_i, mode=mode)`` with s_i = seed + i (a list `seed` is taken as is).
+
+        The low-resolution net decodes every utterance as one ragged row (stream 0, seed s_i).  networks/vocode_plan.py folds every
+        utterance as `_inference_batch` does and sorts the rows (utterance, chunk c; stream c, seed s_i) longest first into launches of
+        at most `max_rows` rows (default: the CU count rounded down to a multiple of 8, which keeps the tile kernel eligible); one
+        ragged high-resolution decode per launch.  Fold and un-fold are torch gathers on the device."""
+        from .vocode_plan import plan_vocode
+        if mode not in ('philox', 'argmax'):
+            raise ValueError("synthesize_batch: mode must be 'philox' or 'argmax', got %r" % (mode,))
+        with torch.no_grad():
+            dev = self._wavernn_lr._get_device()
+            mels = [torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mels]
+            for m in mels:
+                if m.dim() != 2 or m.shape[0] < 1:
+                    raise ValueError('synthesize_batch: every mel is [T, num_mels] with T >= 1, got %s' % (tuple(m.shape),))
+            if isinstance(seed, (list, tuple)):
+                seeds = [int(s) for s in seed]
+            else:
+                if seed is None:
+                    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if mode == 'philox' else 0
+                seeds = [int(seed) + i for i in range(len(mels))]
+            if max_rows is None:
+                max_rows = max(8, torch.cuda.get_device_properties(dev).multi_processor_count // 8 * 8)
+            plan = plan_vocode([int(m.shape[0]) for m in mels], seeds, num_batches=num_batches, max_rows=max_rows,
+                               upsample=self._upsample, upsample_low=self._upsample_low)
+            per_frame = self._upsample // self._upsample_low
+            mel_src = torch.cat([torch.full((1, mels[0].shape[1]), -5.0, dtype=torch.float32, device=dev)] + mels, dim=0)
+            # (a) low-resolution net
+            x_lr = [None] * len(mels)
+            for li, launch in enumerate(plan.lr_launches):
+                lengths, sd, st = plan.lr_tables(li)
+                m = mel_src[torch.from_numpy(plan.lr_mel_index(li)).to(dev)]
+                _, wav, _, _ = self._wavernn_lr.decode({'mel': m}, mode=mode, seed=0, lengths=lengths, seeds=sd, streams=st)
+                for r, i in enumerate(launch):
+                    x_lr[i] = wav[r, :plan.utts[i].T * per_frame]
+            low_src = torch.cat([torch.zeros(1, dtype=torch.float32, device=dev)] + x_lr)
+            # (b)-(d) folded high-resolution rows, one ragged decode per launch
+            outs = []
+            for li in range(len(plan.launches)):
+                im, il = plan.fold_index(li)
+                fr, ll, sd, st = plan.hr_tables(li)
+                X = {'mel': mel_src[torch.from_numpy(im).to(dev)], 'x_low': low_src[torch.from_numpy(il).to(dev)]}
+                _, wav, _, _ = self._wavernn_hr.decode(X, mode=mode, seed=0, lengths=fr, low_lengths=ll, seeds=sd, streams=st)
+                assert wav.shape[1] == plan.launch_width(li)
+                outs.append(wav.reshape(-1))
+            flat = torch.cat(outs)
+            x_hr = [flat[torch.from_numpy(ix).to(dev)] for ix in plan.unfold_index()]
+            self.last_plan = plan
+        return list(zip(x_lr, x_hr))
+
+    def synthesize_batch(self, mels, num_batches=20, max_rows=None, seed=None, mode='philox'):
+        """``_synthesize_batch_device`` with numpy results: a list of (x_lr [24 T_i], x_hr) pairs in input order."""
+        return [(a.cpu().numpy(), b.cpu().numpy())
+                for a, b in self._synthesize_batch_device(mels, num_batches=num_batches, max_rows=max_rows, seed=seed, mode=mode)]
+
     # ---- the LightningModule surface of vocoder.py:133-176 (pl.Trainer.fit(model) in the reference's scripts/train_vocoder.py) ----
     def configure_optimizers(self):
         """vocoder.py:169-173: two Adam optimizers (low-resolution net first)"""
