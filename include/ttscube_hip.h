@@ -645,6 +645,16 @@ int ttsc_melar_set_weights(ttsc_melar* m, const float* w_ih1, int64_t ld1, const
 int32_t ttsc_melar_split_status(void);
 int ttsc_melar_decode(const ttsc_melar* m, const float* xg1_dev, int32_t B, int32_t S, const float* masks_dev, uint64_t seed,
                       const int32_t* steps_dev, float* y_dev, void* stream);
+/* The split factor ttsc_melar_decode picks for B rows on the current device (env cap included); 0 for a bad argument. */
+int32_t ttsc_melar_members(const ttsc_melar* m, int32_t B);
+/* The ragged entry of a batched synthesis: one Philox key per row.  keys_dev uint64 [B] on the device (required when masks_dev is NULL):
+ * row b draws its masks with key keys[b] and counter (unit >> 2, t, 0, layer) — the row index is NOT in the counter, so row b gets exactly
+ * the masks ttsc_melar_decode(B = 1, seed = keys[b]) draws, wherever it stands in the batch, and every split member of a row draws the same.
+ * steps_dev is required.  members: 0 = the rule of ttsc_melar_decode for this B; 1, 2, 4 or 8 force that split — refused (TTSC_EINVAL,
+ * nothing launched) when the sizes do not split that way, when members * B exceeds the CU count (the members of a row spin on each other
+ * and must be co-resident) or when B > 1024 with members > 1.  Row b is bit-identical to its solo decode at the same split. */
+int ttsc_melar_decode_ragged(const ttsc_melar* m, const float* xg1_dev, int32_t B, int32_t S, const float* masks_dev,
+                             const uint64_t* keys_dev, const int32_t* steps_dev, int32_t members, float* y_dev, void* stream);
 void ttsc_melar_destroy(ttsc_melar* m);
 
 /* Device-side duration -> alignment (row f2 of SURVEY.md §8; replaces the host round trip of

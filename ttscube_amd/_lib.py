@@ -243,6 +243,9 @@ SIGNATURES = {
     'ttsc_melar_set_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 11),
     'ttsc_melar_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    'ttsc_melar_members': (C.c_int32, [C.c_void_p, C.c_int32]),
+    'ttsc_melar_decode_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p]),
     'ttsc_melar_destroy': (None, [C.c_void_p]),
     'ttsc_bn_tanh_dropout_train_forward': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_void_p, C.c_uint64, C.c_int32]
                                            + [C.c_void_p] * 4),

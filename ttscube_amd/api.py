@@ -11,7 +11,10 @@ New on top of the reference (B=1 only): ``synthesize_batch`` runs many sentences
 
 A model trained with ``conditioning: fasttext:<lang>`` (the yaml's key) needs the word-vector table it was trained with: ``word_vectors=`` takes a path
 (.vec / .npz) or a ``WordVectors``; by default ``<model_path>.vectors.npz`` (what the trainer writes: the corpus vocabulary) or ``<model_path>.vec`` is read when present.  The front end's ``words`` are
-looked up there; at run time a sentence has no left or right context, so ``x_phon2word`` is the front end's ``phon2word`` itself."""
+looked up there; at run time a sentence has no left or right context, so ``x_phon2word`` is the front end's ``phon2word`` itself.
+
+``TTSCubeTwoStage(textcoder_path, vocoder)`` (not in the reference) is the same interface over the two-stage path: CubenetTextcoder -> mel -> a HiFi-GAN generator
+checkpoint (or a Griffin-Lim / WaveRNN vocoder object), one sentence or a list, reproducible per sentence through ``seed``."""
 import os
 from pathlib import Path
 
@@ -213,3 +216,154 @@ class TTSCube:
         n = len(items)
         lo, hi = rank * n // world_size, (rank + 1) * n // world_size
         return items[lo:hi]
+
+
+class TTSCubeTwoStage:
+    """Text to speech over the two-stage path (NOT in the reference, whose only consumer of a trained Textcoder walks a processed dev set:
+    io_utils/runtime.py::synthesize_devset): text -> phones -> CubenetTextcoder -> log10-mel -> natural-log mel -> vocoder.
+
+    textcoder_path: the base scripts/train_textcoder.py writes — `<base>.yaml` (pframes, sample_rate, hop_size), `<base>.encodings`, `<base>.best`
+    (else `<base>.last`).  vocoder: a HiFi-GAN generator checkpoint path (io_utils.runtime.load_generator_checkpoint: config.json beside it), or
+    any object with synthesize_devset's `vocoder` contract (natural-log mel [B, 80, F] on the device -> audio [B, 1, L] on the device:
+    io_utils.vocoder.GriffinLimVocoder / WaveRNNVocoder).  The front end is TTSCube's (phonemizer_path / text2feat / the phone-string reader).
+
+    The PreNet's dropout is always on (cube/networks/modules.py:159-164), so a sentence's audio is a function of (text, speaker, seed): `seed` is
+    the Philox key of its AR decode.  Sentence i of a `synthesize_batch` list gets key seed + i wherever it lands after length-sorting and
+    grouping, and equals `tts(texts[i], seed=seed + i)` (DESIGN.md §9m states the limit of that equality)."""
+
+    def __init__(self, textcoder_path: str, vocoder, phonemizer_path: str = None, text2feat=None, device='cuda:0'):
+        from .io_utils.io_textcoder import TextcoderEncodings
+        from .networks.textcoder import CubenetTextcoder
+        conf = yaml.load(open('{0}.yaml'.format(textcoder_path)), yaml.Loader) or {}
+        self.sample_rate = int(conf.get('sample_rate', 24000))
+        self._device = torch.device(device)
+        self._encodings = TextcoderEncodings('{0}.encodings'.format(textcoder_path))
+        ckpt = next((p for p in ('{0}.best'.format(textcoder_path), '{0}.last'.format(textcoder_path)) if os.path.exists(p)), None)
+        if ckpt is None:
+            raise FileNotFoundError('%s.best / %s.last: no Textcoder checkpoint (scripts/train_textcoder.py writes them)' % (textcoder_path, textcoder_path))
+        self._model = CubenetTextcoder(self._encodings, pframes=int(conf.get('pframes', 3)))
+        self._model.load(ckpt)
+        self._model.eval()
+        self._model.to(self._device)
+        if isinstance(vocoder, (str, os.PathLike)):
+            from .io_utils.runtime import load_generator_checkpoint
+            vocoder = load_generator_checkpoint(str(vocoder)).to(self._device)
+        self._vocoder = vocoder
+        import inspect
+        try:
+            fn = vocoder.forward if isinstance(vocoder, torch.nn.Module) else vocoder.__call__
+            self._takes_frames = 'frames' in inspect.signature(fn).parameters
+        except (TypeError, ValueError):
+            self._takes_frames = False
+        self._is_generator = hasattr(vocoder, 'finish_range_check') and hasattr(vocoder, 'range_check_pending')
+        self._text2feat = TTSCube._make_text2feat(phonemizer_path, text2feat, device)
+        self.last_stats = {}
+
+    # ---- text -> batch dict ---------------------------------------------------------------------------------------------------------------
+    def _phones(self, text, feats=None):
+        return list((self._text2feat(text) if feats is None else feats)['phones'])
+
+    def _speaker_id(self, speaker):
+        """TextcoderCollate's id + 1; a speaker the encodings do not know is the padding row 0 ('none': TTSCube's default)"""
+        return self._encodings.speaker2int[speaker] + 1 if speaker in self._encodings.speaker2int else 0
+
+    def _collate(self, phones, speakers):
+        """x_char (phone id + 1, unknown phones 0 — io_textcoder.TextcoderCollate), x_speaker, and x_len: id 0 is both padding and an unknown phone"""
+        n = max(max((len(p) for p in phones), default=0), 1)
+        x_char = torch.zeros((len(phones), n), dtype=torch.long)
+        for b, ps in enumerate(phones):
+            for j, ph in enumerate(ps):
+                x_char[b, j] = self._encodings.phon2int[ph] + 1 if ph in self._encodings.phon2int else 0
+        x_speaker = torch.tensor([[self._speaker_id(s)] for s in speakers], dtype=torch.long)
+        return {'x_char': x_char, 'x_speaker': x_speaker, 'x_len': torch.tensor([len(p) for p in phones], dtype=torch.long)}
+
+    # ---- mel -> audio ---------------------------------------------------------------------------------------------------------------------
+    def _vocode(self, mel_cm, frames, check):
+        """log10-mel [B, 80, Fmax] (zeros past frames[b]) -> list of B 1-D float32 device tensors, each its sentence's own samples (empty for a
+        sentence without a frame).  mel -> torch.log(10 ** mel) as synthesize_devset does; with a vocoder whose call takes `frames=` the rows
+        that have frames go in ONE ragged call, otherwise every sentence is vocoded on its own trimmed mel."""
+        B = mel_cm.shape[0]
+        out = [torch.zeros(0, dtype=torch.float32, device=mel_cm.device) for _ in range(B)]
+        act = [b for b in range(B) if frames[b] > 0]
+        if not act:
+            return out
+        ln = torch.log(10 ** mel_cm)
+        voc = self._vocoder
+        if not self._takes_frames:
+            for b in act:
+                out[b] = voc(ln[b:b + 1, :, :frames[b]].contiguous()).detach().reshape(-1)
+            return out
+        if len(act) < B:
+            ln = ln.index_select(0, torch.tensor(act, dtype=torch.int64, device=ln.device))
+        fr = [frames[b] for b in act]
+        ln = ln[:, :, :max(fr)].contiguous()
+        if self._is_generator:
+            wav = voc(ln, frames=fr, check=check).detach()
+            lens = [int(voc.out_len(f)) for f in fr]
+        else:
+            wav = voc(ln, frames=fr).detach()
+            lens = list(getattr(voc, 'last_lengths', None) or [wav.shape[-1]] * len(act))
+        for j, b in enumerate(act):
+            out[b] = wav[j, 0, :lens[j]]
+        return out
+
+    def _run(self, X, seeds, members=None, max_rows=None):
+        """one padded batch -> list of per-sentence device waveforms; the generator's range guard runs deferred and its verdict is collected right
+        behind the forward's last use, as TTSCube.__call__ collects it — a tripped guard redoes the vocoding with the self-repairing check"""
+        mel, frames, st = self._model.inference_batch(X, seeds=seeds, members=members, max_rows=max_rows, channel_major=True, return_stats=True)
+        self.last_stats = st
+        if not self._is_generator:
+            return self._vocode(mel, frames, None)
+        gen, tripped = self._vocoder, False
+        try:
+            wavs = self._vocode(mel, frames, 'deferred')
+        finally:
+            if gen.range_check_pending():
+                tripped = gen.finish_range_check(raise_on_trip=False)
+        if tripped:
+            wavs = self._vocode(mel, frames, 'sync')
+        return wavs
+
+    @staticmethod
+    def _seed(seed):
+        return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+
+    @staticmethod
+    def _int16(wav):
+        return np.asarray(wav.detach().cpu().numpy().reshape(-1) * 32767, dtype=np.int16)
+
+    def __call__(self, text, speaker='none', seed=None):
+        """one sentence -> int16 audio at the yaml's sample rate; `seed`: the key of the PreNet's dropout masks (None: drawn from torch's generator)"""
+        with torch.no_grad():
+            phones = self._phones(text)
+            if not phones:                      # (nothing to say: no batch row is made of it)
+                return np.zeros(0, dtype=np.int16)
+            return self._int16(self._run(self._collate([phones], [speaker]), [self._seed(seed)])[0])
+
+    def synthesize_batch(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None):
+        """Many sentences -> list of int16 arrays (same order).  Sentences are sorted by phone count and run in padded batches of up to `max_batch`;
+        sentence i gets key seed + i, so entry i equals `self(texts[i], seed=seed + i)` whatever the grouping.  members / max_rows: the AR launch
+        shape (CubenetTextcoder._ar_decode_batch) — the defaults keep the single call's bits."""
+        return [self._int16(w) for w in self._synthesize_batch_device(texts, speaker, max_batch, seed, members, max_rows)]
+
+    def _synthesize_batch_device(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None):
+        """`synthesize_batch` without the copy to the host: list of 1-D float32 device tensors in [-1, 1], input order, each trimmed to its own samples"""
+        texts = list(texts)
+        speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
+        seed = self._seed(seed)
+        feats = self._text2feat.batch(texts) if hasattr(self._text2feat, 'batch') else [None] * len(texts)
+        phones = [self._phones(t, f) for t, f in zip(texts, feats)]
+        order = sorted((i for i in range(len(texts)) if phones[i]), key=lambda i: len(phones[i]))
+        out = [torch.zeros(0, dtype=torch.float32, device=self._device) for _ in texts]      # (a sentence without a phone stays empty and takes no row)
+        stats = {'launches': 0, 'max_steps': 0}
+        with torch.no_grad():
+            for s in range(0, len(order), max(1, int(max_batch))):
+                ids = order[s:s + max(1, int(max_batch))]
+                X = self._collate([phones[i] for i in ids], [speakers[i] for i in ids])
+                for i, w in zip(ids, self._run(X, [seed + i for i in ids], members, max_rows)):
+                    out[i] = w
+                stats = {'launches': stats['launches'] + self.last_stats['launches'], 'max_steps': max(stats['max_steps'], self.last_stats['max_steps'])}
+        self.last_stats = stats
+        return out
+
+    shard = staticmethod(TTSCube.shard)

@@ -9,7 +9,9 @@
 //   * thread j owns hidden unit j of BOTH LSTM layers (its 4 gate rows per matrix are streamed from L2 as packed 16-byte
 //     loads with explicit double-buffered prefetch, c_j stays in a register, h in LDS); PreNet rows and output rows are
 //     owned by the first 256 / 240 threads; 5 workgroup barriers per step, no inter-workgroup communication.
-// Dropout masks: injected ({0,1} floats, parity tests) or drawn in-kernel from Philox-4x32-10 counters (step, layer, unit).
+// Dropout masks: injected ({0,1} floats, parity tests) or drawn in-kernel from Philox-4x32-10 counters (step, layer, unit) — under the launch's
+// seed with the row index in the counter (ttsc_melar_decode), or under a key of the row's own (ttsc_melar_decode_ragged: a batched synthesis
+// whose rows keep the bits of their solo decodes).
 #include "common.hpp"
 #include "../../include/ttscube_math.h"
 #include "handoff.hpp"
@@ -36,6 +38,7 @@ struct MelArArgs {
     int B, S, H, P, M, O;
     float init_mel;       // -5
     unsigned long long seed;
+    const unsigned long long* keys;   // [B] per-row Philox keys or null (launch-wide `seed`, row index in the counter)
 };
 
 __global__ __launch_bounds__(512) void melar_kernel(MelArArgs a) {
@@ -49,6 +52,9 @@ __global__ __launch_bounds__(512) void melar_kernel(MelArArgs a) {
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
     const int nsteps = a.steps ? a.steps[b] : a.S;
+    // Philox stream of this row: its own key with counter word 2 = 0 (the row decoded alone under that key), else the launch's seed and the row index
+    const unsigned long long key = a.keys ? a.keys[b] : a.seed;
+    const uint32_t crow = a.keys ? 0u : (uint32_t)b;
     for (int i = tid; i < 4 * H; i += blockDim.x) sm[i] = 0.f;
     for (int i = tid; i < M; i += blockDim.x) lm[i] = a.init_mel;
     float c1 = 0.f, c2 = 0.f;
@@ -59,7 +65,7 @@ __global__ __launch_bounds__(512) void melar_kernel(MelArArgs a) {
         auto mask = [&](int layer, int unit) -> float {
             if (a.masks) return a.masks[(((size_t)b * a.S + t) * 2 + layer) * P + unit];
             uint32_t r4[4];
-            ttsc_philox4x32((uint32_t)(unit >> 2), (uint32_t)t, (uint32_t)b, (uint32_t)layer, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r4);
+            ttsc_philox4x32((uint32_t)(unit >> 2), (uint32_t)t, crow, (uint32_t)layer, (uint32_t)key, (uint32_t)(key >> 32), r4);
             return (r4[unit & 3] & 1u) ? 1.f : 0.f;   // Bernoulli(0.5)
         };
         // ---- PreNet layer 1: relu(W1 . last_mel + b1) * mask * 2 ----
@@ -149,6 +155,8 @@ __global__ __launch_bounds__(512) void melar_split_kernel(MelArSplitArgs s) {
     const bool owner = ks == 0;
     const int KP = P / KS, KH = H / KS;
     const int nsteps = a.steps ? a.steps[b] : a.S;
+    const unsigned long long key = a.keys ? a.keys[b] : a.seed;   // (as in melar_kernel: every member of the row draws the same masks)
+    const uint32_t crow = a.keys ? 0u : (uint32_t)b;
     unsigned* cnt = s.cnt + b;
     float* xh1 = s.xh + (size_t)b * 4 * H;
     float* xh2 = xh1 + 2 * H;
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(512) void melar_split_kernel(MelArSplitArgs s) {
         auto mask = [&](int layer, int unit) -> float {
             if (a.masks) return a.masks[(((size_t)b * a.S + t) * 2 + layer) * P + unit];
             uint32_t r4[4];
-            ttsc_philox4x32((uint32_t)(unit >> 2), (uint32_t)t, (uint32_t)b, (uint32_t)layer, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r4);
+            ttsc_philox4x32((uint32_t)(unit >> 2), (uint32_t)t, crow, (uint32_t)layer, (uint32_t)key, (uint32_t)(key >> 32), r4);
             return (r4[unit & 3] & 1u) ? 1.f : 0.f;
         };
         float xv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -305,6 +313,13 @@ extern "C" int ttsc_melar_set_weights(ttsc_melar* m, const float* w_ih1, int64_t
 }
 
 
+// shape conditions of a split over G workgroups: >= 32 units per member, 512 threads = (unit, k-slice) pairs, k-slices of 8-float blocks
+static bool melar_split_level_ok(int G, int H, int P) {
+    if (H % G != 0 || H / G < 32 || 512 % (H / G) != 0) return false;
+    const int HU = H / G, KS = 512 / HU;
+    return H % KS == 0 && (H / KS) % 8 == 0 && P % KS == 0 && (P / KS) % 8 == 0;
+}
+
 // split factor for the AR decoder: 15.5 MB of weights per step make G = 8 the measured optimum for one utterance
 // (G = 1 / 2 / 4 / 8: 12.1 / 9.5 / 8.0 / 5.9 ms for 58 steps), >= 32 units per member, all workgroups co-resident
 static int melar_split_members(int B, int H, int P) {
@@ -312,11 +327,7 @@ static int melar_split_members(int B, int H, int P) {
     int gmax = 8;
     if (const char* ev = getenv("TTSC_MELAR_SPLIT")) gmax = atoi(ev);
     int G = 1;
-    while (G * 2 <= gmax && (long)G * 2 * B <= cus && H % (G * 2) == 0 && H / (G * 2) >= 32 && 512 % (H / (G * 2)) == 0) {
-        const int HU = H / (G * 2), KS = 512 / HU;
-        if (H % KS != 0 || (H / KS) % 8 != 0 || P % KS != 0 || (P / KS) % 8 != 0) break;
-        G *= 2;
-    }
+    while (G * 2 <= gmax && (long)G * 2 * B <= cus && melar_split_level_ok(G * 2, H, P)) G *= 2;
     return G;
 }
 
@@ -324,21 +335,21 @@ static int melar_split_members(int B, int H, int P) {
 // (sticky until read).  Synchronises the device.  The exchange area [B][4][H] + counters live in one HandoffArea per (device, stream).
 extern "C" int32_t ttsc_melar_split_status(void) { return handoff_status("melar"); }
 
-extern "C" int ttsc_melar_decode(const ttsc_melar* m, const float* xg1_dev, int32_t B, int32_t S, const float* masks_dev,
-                                 uint64_t seed, const int32_t* steps_dev, float* y_dev, void* stream) {
-    TTSC_REQUIRE(m && xg1_dev && y_dev, "ttsc_melar_decode: null argument");
-    TTSC_REQUIRE(B > 0 && S > 0, "ttsc_melar_decode: bad B/S");
-    if (!m->w_pn2) {
-        set_error("ttsc_melar_decode: weights not set");
-        return TTSC_ESTATE;
-    }
-    MelArArgs a{xg1_dev, m->w_p2l, m->w_hh1, m->w_ih2, m->w_hh2, m->b2, m->w_out, m->b_out, m->w_pn1, m->b_pn1, m->w_pn2, m->b_pn2,
-                masks_dev, steps_dev, y_dev, B, S, m->H, m->P, m->M, m->O, -5.0f, seed};
-    const int G = B <= 1024 ? melar_split_members(B, m->H, m->P) : 1;
+extern "C" int32_t ttsc_melar_members(const ttsc_melar* m, int32_t B) {
+    if (!m || B <= 0) return 0;
+    return B <= 1024 ? melar_split_members(B, m->H, m->P) : 1;
+}
+
+// one launch of the decode loop at split factor G (1 = melar_kernel); the caller has checked G against the shapes and the CU count
+static int melar_launch(const ttsc_melar* m, const MelArArgs& a, int G, void* stream, const char* who) {
+    const int B = a.B;
     if (G > 1) {
         hipStream_t st = (hipStream_t)stream;
         HandoffArea* ar = handoff_area("melar", st, 1024, (size_t)B * 4 * 512 * sizeof(float));
-        TTSC_REQUIRE(ar, "ttsc_melar_decode: cannot allocate the exchange area");
+        if (!ar) {
+            set_error("%s: cannot allocate the exchange area", who);
+            return TTSC_EINVAL;
+        }
         TTSC_HIP_CHECK(ar->rearm(st));   // counters and this launch's abort word restart at zero; the sticky copy stays
         MelArSplitArgs sa{};
         sa.a = a;
@@ -366,4 +377,48 @@ extern "C" int ttsc_melar_decode(const ttsc_melar* m, const float* xg1_dev, int3
         return TTSC_EHIP;
     }
     return TTSC_OK;
+}
+
+extern "C" int ttsc_melar_decode(const ttsc_melar* m, const float* xg1_dev, int32_t B, int32_t S, const float* masks_dev,
+                                 uint64_t seed, const int32_t* steps_dev, float* y_dev, void* stream) {
+    TTSC_REQUIRE(m && xg1_dev && y_dev, "ttsc_melar_decode: null argument");
+    TTSC_REQUIRE(B > 0 && S > 0, "ttsc_melar_decode: bad B/S");
+    if (!m->w_pn2) {
+        set_error("ttsc_melar_decode: weights not set");
+        return TTSC_ESTATE;
+    }
+    MelArArgs a{xg1_dev, m->w_p2l, m->w_hh1, m->w_ih2, m->w_hh2, m->b2, m->w_out, m->b_out, m->w_pn1, m->b_pn1, m->w_pn2, m->b_pn2,
+                masks_dev, steps_dev, y_dev, B, S, m->H, m->P, m->M, m->O, -5.0f, seed, nullptr};
+    return melar_launch(m, a, B <= 1024 ? melar_split_members(B, m->H, m->P) : 1, stream, "ttsc_melar_decode");
+}
+
+// The ragged entry: per-row Philox keys (row b draws what ttsc_melar_decode(B = 1, seed = keys[b]) draws: the row index is not in the counter) and a
+// split the caller may force.  A forced split is checked HERE, before anything is launched: the members of a row spin on each other, so all
+// members * B workgroups must be co-resident.
+extern "C" int ttsc_melar_decode_ragged(const ttsc_melar* m, const float* xg1_dev, int32_t B, int32_t S, const float* masks_dev,
+                                        const uint64_t* keys_dev, const int32_t* steps_dev, int32_t members, float* y_dev, void* stream) {
+    TTSC_REQUIRE(m && xg1_dev && y_dev, "ttsc_melar_decode_ragged: null argument");
+    TTSC_REQUIRE(B > 0 && S > 0, "ttsc_melar_decode_ragged: bad B/S");
+    TTSC_REQUIRE(steps_dev, "ttsc_melar_decode_ragged: steps_dev is required");
+    TTSC_REQUIRE(masks_dev || keys_dev, "ttsc_melar_decode_ragged: keys_dev is required when masks_dev is NULL");
+    TTSC_REQUIRE(members == 0 || members == 1 || members == 2 || members == 4 || members == 8,
+                 "ttsc_melar_decode_ragged: members must be 0, 1, 2, 4 or 8 (got %d)", members);
+    if (!m->w_pn2) {
+        set_error("ttsc_melar_decode_ragged: weights not set");
+        return TTSC_ESTATE;
+    }
+    int G = members;
+    if (G == 0) {
+        G = B <= 1024 ? melar_split_members(B, m->H, m->P) : 1;
+    } else if (G > 1) {
+        for (int g = 2; g <= G; g *= 2)
+            TTSC_REQUIRE(melar_split_level_ok(g, m->H, m->P), "ttsc_melar_decode_ragged: sizes H=%d P=%d do not split over %d workgroups", m->H, m->P, G);
+        TTSC_REQUIRE(B <= 1024, "ttsc_melar_decode_ragged: a split launch takes at most 1024 rows (got %d)", B);
+        const int cus = device_cus();
+        TTSC_REQUIRE((long)G * B <= cus, "ttsc_melar_decode_ragged: %d members x %d rows exceed the %d CUs (the members of a row must be co-resident)",
+                     G, B, cus);
+    }
+    MelArArgs a{xg1_dev, m->w_p2l, m->w_hh1, m->w_ih2, m->w_hh2, m->b2, m->w_out, m->b_out, m->w_pn1, m->b_pn1, m->w_pn2, m->b_pn2,
+                masks_dev, steps_dev, y_dev, B, S, m->H, m->P, m->M, m->O, -5.0f, 0ull, (const unsigned long long*)keys_dev};
+    return melar_launch(m, a, G, stream, "ttsc_melar_decode_ragged");
 }

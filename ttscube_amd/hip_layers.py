@@ -76,7 +76,9 @@ class Conv1dHip:
         return int(_lib.lib().ttsc_conv1d_out_len(self._h, Lin))
 
     def __call__(self, x, resid=None, out=None, in_scale=1.0, in_slope=1.0, out_scale=1.0, act=None, accumulate=False,
-                 gate=None, gate_slope=1.0):
+                 gate=None, gate_slope=1.0, in_len=None, out_len=None):
+        """in_len / out_len (int32 device tensors [B], both or neither): the ragged call (ttsc_conv1d_forward_ragged) — input beyond in_len[b]
+        reads as zero, as it does for the utterance run alone; what lies beyond out_len[b] in the output is unspecified."""
         if not x.is_cuda:
             raise _lib.TTSCError('Conv1dHip: input must live on a HIP device; no CPU path')
         x = x.float().contiguous()
@@ -96,7 +98,17 @@ class Conv1dHip:
             assert gate.is_contiguous() and gate.dtype == torch.float32 and tuple(gate.shape) == tuple(out.shape)
         ep = _lib.Conv1dEpilogue(in_scale, in_slope, out_scale, ACT[act], int(accumulate),
                                  gate.data_ptr() if gate is not None else None, gate_slope)
+        if (in_len is None) != (out_len is None):
+            raise _lib.TTSCError('Conv1dHip: in_len and out_len go together')
         with _lib.on_device(x.device):
+            if in_len is not None:
+                for t in (in_len, out_len):
+                    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+                _lib.check(_lib.lib().ttsc_conv1d_forward_ragged(self._h, _lib.dev_ptr(x), B, Lin, _lib.dev_ptr(out),
+                                                                 _lib.dev_ptr(resid) if resid is not None else None, C.byref(ep),
+                                                                 _lib.dev_ptr(in_len), _lib.dev_ptr(out_len), _lib.current_stream()),
+                           'ttsc_conv1d_forward_ragged')
+                return out
             _lib.check(_lib.lib().ttsc_conv1d_forward(self._h, _lib.dev_ptr(x), B, Lin, _lib.dev_ptr(out),
                                                       _lib.dev_ptr(resid) if resid is not None else None,
                                                       C.byref(ep), _lib.current_stream()), 'ttsc_conv1d_forward')

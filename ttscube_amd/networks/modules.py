@@ -298,17 +298,23 @@ class PostNet(nn.Module):
                                   (self.network[8].conv, self.network[9]), (self.network[12].conv, self.network[13]),
                                   (self.network[16].conv, None)])
 
-    def forward(self, x, add_residual=False):
-        """x [B, F, 80] -> [B, F, 80]; add_residual=True returns x + postnet(x) (textcoder.py:186-187) in one epilogue."""
+    def forward(self, x, add_residual=False, lengths=None, channel_major=False):
+        """x [B, F, 80] -> [B, F, 80]; add_residual=True returns x + postnet(x) (textcoder.py:186-187) in one epilogue.
+        lengths (frames per row of a padded batch): every layer reads zeros past a row's own last frame, as it does for the row run alone
+        (ttsc_conv1d_forward_ragged), and the result is zero there.  channel_major=True hands back [B, 80, F] — what a vocoder takes."""
         if self.training:
             raise _lib.TTSCError('PostNet: the HIP path implements eval-mode BatchNorm/Dropout (call .eval())')
         hs = self._stack.sync()
         xc = x.float().permute(0, 2, 1).contiguous()
+        ln = _lib.lengths_dev(lengths, xc.device)
         h = xc
         for c in hs[:-1]:
-            h = c(h, act='tanh')
-        y = hs[-1](h, resid=xc if add_residual else None)
-        return y.permute(0, 2, 1).contiguous()
+            h = c(h, act='tanh', in_len=ln, out_len=ln)
+        y = hs[-1](h, resid=xc if add_residual else None, in_len=ln, out_len=ln)
+        if ln is not None:
+            # (the kernels leave the tail of a row's last tile and the skipped tiles unspecified)
+            y = torch.where(torch.arange(y.shape[2], device=y.device)[None, None, :] < ln[:, None, None], y, torch.zeros((), device=y.device))
+        return y if channel_major else y.permute(0, 2, 1).contiguous()
 
 
 class PreNet(nn.Module):

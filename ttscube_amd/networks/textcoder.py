@@ -67,9 +67,10 @@ class CubenetTextcoder(nn.Module):
         hd = self._lstm('_dur_rnn')(h, lengths=lengths)
         return h, linear_hip(hd, self._dur_output.linear_layer.weight, self._dur_output.linear_layer.bias)
 
-    def inference(self, X, dropout_masks=None):
-        """textcoder.py:140-189 (B=1 like the reference).  dropout_masks: optional [steps, 2, 1, 256] {0,1} PreNet masks
-        (parity tests); otherwise drawn from torch's device generator.  Returns post-net mel [1, F, 80] (log10)."""
+    def inference(self, X, dropout_masks=None, seed=None):
+        """textcoder.py:140-189 (B=1 like the reference; `inference_batch` takes a padded batch).  dropout_masks: optional [steps, 2, 1, 256]
+        {0,1} PreNet masks (parity tests); otherwise drawn in the kernel from Philox with key `seed` (None: a key from torch's generator).
+        Returns post-net mel [1, F, 80] (log10)."""
         dev = self._get_device()
         x_char, x_speaker = X['x_char'].to(dev), X['x_speaker'].to(dev)
         assert x_char.shape[0] == 1, 'CubenetTextcoder.inference follows the reference: one utterance per call'
@@ -80,7 +81,7 @@ class CubenetTextcoder(nn.Module):
             if h.shape[1] == 0:
                 return torch.zeros((1, 0, 80), device=dev)
             h = self._lstm('_rnn_overlay')(h)
-            mel = self._ar_decode(h, dropout_masks)
+            mel = self._ar_decode(h, dropout_masks, seed=seed)
             out = self._postnet(mel, add_residual=True)
             _lib.check_split_status('CubenetTextcoder.inference')
             return out
@@ -109,28 +110,151 @@ class CubenetTextcoder(nn.Module):
         self._hip['_melar_sig'] = sig
         return hnd
 
-    def _ar_decode(self, h, dropout_masks=None, steps=None, seed=None, out=None):
-        """textcoder.py:174-185 as ONE persistent kernel launch (csrc/melar.hip).  h: overlay states [B, S, 1024]; dropout_masks
-        [S, 2, B, 256] or None (in-kernel Philox from seed); steps [B] or None (all S); out: optional device tensor [B, S, 80 * pframes]
-        the kernel writes (every element of it)."""
-        hnd = self._melar_handle()
-        B, S, _ = h.shape
+    def _ar_xg1(self, h):
+        """the hoisted layer-1 input projection of all rows and steps: overlay states [B, S, 1024] -> [B, S, 4H]"""
         r = self._mel_rnn
         n_ov = r.weight_ih_l0.shape[1] - 256
-        xg1 = linear_hip(h, r.weight_ih_l0[:, :n_ov].contiguous(), r.bias_ih_l0 + r.bias_hh_l0)    # hoisted input projection
+        return linear_hip(h, r.weight_ih_l0[:, :n_ov].contiguous(), r.bias_ih_l0 + r.bias_hh_l0)
+
+    def _ar_decode(self, h, dropout_masks=None, steps=None, seed=None, out=None, seeds=None, members=None):
+        """textcoder.py:174-185 as ONE persistent kernel launch (csrc/melar.hip).  h: overlay states [B, S, 1024]; dropout_masks
+        [S, 2, B, 256] or None (in-kernel Philox from seed); steps [B] or None (all S); out: optional device tensor [B, S, 80 * pframes]
+        the kernel writes (every element of it).
+        seeds (B integers < 2**63 or a device int64 tensor [B]) selects the ragged entry (ttsc_melar_decode_ragged): row b draws the masks
+        of its solo decode with seed = seeds[b], wherever it stands in the batch; members (None / 0: the dispatcher's rule for B rows; 1, 2,
+        4, 8: that split, refused when members * B workgroups cannot be co-resident) belongs to that entry."""
+        B, S, _ = h.shape
         y = torch.empty((B, S, 80 * self._pframes), dtype=torch.float32, device=h.device) if out is None else out
         assert y.shape == (B, S, 80 * self._pframes) and y.dtype == torch.float32 and y.is_contiguous() and y.device == h.device
+        if seeds is None and members is not None:
+            raise _lib.TTSCError('CubenetTextcoder._ar_decode: members= belongs to the per-row-key entry (give seeds=)')
+        self._ar_launch(self._ar_xg1(h), dropout_masks, steps, seed, seeds, members, y)
+        return y.reshape(B, S * self._pframes, 80).contiguous()
+
+    @staticmethod
+    def _row_keys(seeds, B, dev):
+        """per-row Philox keys as a device int64 tensor [B] (the kernel reads the same 64 bits unsigned)"""
+        if torch.is_tensor(seeds):
+            k = seeds.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        else:
+            vals = [int(v) for v in seeds]
+            if any(v < 0 or v >= 2 ** 63 for v in vals):
+                raise _lib.TTSCError('CubenetTextcoder: seeds must be integers in [0, 2**63)')
+            k = torch.tensor(vals, dtype=torch.int64, device=dev)
+        if k.numel() != B:
+            raise _lib.TTSCError('CubenetTextcoder: %d seeds for a batch of %d' % (k.numel(), B))
+        return k
+
+    def _ar_launch(self, xg1, dropout_masks, steps, seed, seeds, members, y):
+        """one launch of the AR kernel on xg1 [B, S, 4H] into y [B, S, O]"""
+        hnd = self._melar_handle()
+        B, S, _ = xg1.shape
+        dev = xg1.device
         m = None
         if dropout_masks is not None:
-            m = torch.as_tensor(dropout_masks).to(h.device).float().reshape(S, 2, B, 256).permute(2, 0, 1, 3).contiguous()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        st = torch.as_tensor(steps, dtype=torch.int32, device=h.device) if steps is not None else None
-        with _lib.on_device(h.device):
-            _lib.check(_lib.lib().ttsc_melar_decode(hnd, _lib.dev_ptr(xg1), B, S, _lib.dev_ptr(m) if m is not None else None,
-                                                    C.c_uint64(seed), _lib.dev_ptr(st) if st is not None else None, _lib.dev_ptr(y),
-                                                    _lib.current_stream()), 'ttsc_melar_decode')
-        return y.reshape(B, S * self._pframes, 80).contiguous()
+            m = torch.as_tensor(dropout_masks).to(dev).float().reshape(S, 2, B, 256).permute(2, 0, 1, 3).contiguous()
+        st = torch.as_tensor(steps, dtype=torch.int32, device=dev).contiguous() if steps is not None else None
+        P = lambda t: _lib.dev_ptr(t) if t is not None else None
+        with _lib.on_device(dev):
+            if seeds is not None:
+                keys = self._row_keys(seeds, B, dev)
+                if st is None:
+                    st = torch.full((B,), S, dtype=torch.int32, device=dev)
+                _lib.check(_lib.lib().ttsc_melar_decode_ragged(hnd, P(xg1), B, S, P(m), P(keys), P(st), int(members or 0), P(y),
+                                                               _lib.current_stream()), 'ttsc_melar_decode_ragged')
+                return
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            _lib.check(_lib.lib().ttsc_melar_decode(hnd, P(xg1), B, S, P(m), C.c_uint64(seed), P(st), P(y), _lib.current_stream()),
+                       'ttsc_melar_decode')
+
+    def ar_members(self, B=1):
+        """the split factor the AR dispatcher picks for B rows on the current device (ttsc_melar_members)"""
+        return int(_lib.lib().ttsc_melar_members(self._melar_handle(), int(B)))
+
+    def _ar_decode_batch(self, h, steps, seeds=None, dropout_masks=None, max_rows=None, members=None):
+        """The AR stage of `inference_batch`: overlay states h [B, S, 1024] with `steps` [B] valid steps per row -> (pre-postnet mel
+        [B, S * pframes, 80], zeros past a row's steps; number of launches).  One hoisted xg1 GEMM, then the launches of
+        textcoder_plan.plan_ar_launches: longest rows first, at most max_rows rows each (default CUs // members: the member workgroups of
+        a launch must all be resident), every launch at the SAME split `members` (default: what one sentence gets alone) — so a row's bits
+        do not depend on the launch it lands in."""
+        from .textcoder_plan import plan_ar_launches
+        B, S, _ = h.shape
+        dev = h.device
+        steps = [int(v) for v in steps]
+        assert len(steps) == B and max(steps, default=0) <= S
+        O = 80 * self._pframes
+        if members is None:
+            with _lib.on_device(dev):
+                members = self.ar_members(1)
+        if max_rows is None:
+            max_rows = max(1, torch.cuda.get_device_properties(dev).multi_processor_count // members)
+        if seeds is None and dropout_masks is None:
+            seeds = torch.randint(0, 2 ** 62, (B,)).tolist()
+        keys = self._row_keys(seeds, B, dev) if seeds is not None else torch.zeros(B, dtype=torch.int64, device=dev)
+        mk = None
+        if dropout_masks is not None:
+            mk = torch.as_tensor(dropout_masks).to(dev).float().reshape(S, 2, B, 256)
+        plan = plan_ar_launches(steps, max_rows)
+        y = torch.zeros((B, S, O), dtype=torch.float32, device=dev)
+        if not plan:
+            return y.reshape(B, S * self._pframes, 80), 0
+        xg1 = self._ar_xg1(h)
+        st_all = torch.tensor(steps, dtype=torch.int32, device=dev)
+        for rows in plan:
+            Sl = steps[rows[0]]                      # (longest first: the launch's horizon)
+            if len(rows) == B and Sl == S and rows == list(range(B)):
+                self._ar_launch(xg1, mk, st_all, None, keys, members, y)
+                continue
+            idx = torch.tensor(rows, dtype=torch.int64, device=dev)
+            yl = torch.empty((len(rows), Sl, O), dtype=torch.float32, device=dev)
+            self._ar_launch(xg1.index_select(0, idx)[:, :Sl].contiguous(), None if mk is None else mk[:Sl].index_select(2, idx),
+                            st_all.index_select(0, idx), None, keys.index_select(0, idx), members, yl)
+            y[idx, :Sl] = yl
+        return y.reshape(B, S * self._pframes, 80), len(plan)
+
+    def inference_batch(self, X, seeds=None, dropout_masks=None, max_rows=None, members=None, channel_major=False, return_stats=False):
+        """A padded batch of sentences -> (post-net mel [B, Fmax, 80] log10, frames [B]): each row holds what `inference` gives for that
+        sentence alone with seed = seeds[b] (zeros past its own frames[b]), wherever the row stands and whichever AR launch it lands in.
+        X: 'x_char' long [B, N] (0 = padding AND an out-of-vocabulary phone: give 'x_len', rule of _char_lengths), 'x_speaker' long [B, 1].
+        seeds: B integers < 2**63 (None: drawn from torch's generator); dropout_masks [S, 2, B, 256] injects the PreNet masks instead
+        (parity tests).  members / max_rows: see _ar_decode_batch.  Rows without a frame are launched nowhere: their mel is empty.
+        channel_major=True returns the mel as [B, 80, Fmax] (what a vocoder takes); return_stats=True appends {'launches', 'max_steps', 'rows', 'mel_ar'}."""
+        dev = self._get_device()
+        x_char, x_speaker = X['x_char'].to(dev), X['x_speaker'].to(dev)
+        B = x_char.shape[0]
+        pf = self._pframes
+        with torch.no_grad():
+            lengths = _lib.DevLengths(_char_lengths(X, x_char), device=dev)
+            h, out_dur = self._text_stack(x_char, x_speaker, lengths)
+            h, steps = _expand_rows(h, align_durations(out_dur, lengths), stride=pf)
+            steps = [int(v) for v in steps]
+            frames = [n * pf for n in steps]
+            S = max(steps) if steps else 0
+            stats = {'launches': 0, 'max_steps': S}
+            if S == 0:
+                out = torch.zeros((B, 80, 0) if channel_major else (B, 0, 80), device=dev)
+                return (out, frames, stats) if return_stats else (out, frames)
+            act = [b for b in range(B) if steps[b] > 0]      # (rows without a frame take part in nothing below)
+            if len(act) < B:
+                idx = torch.tensor(act, dtype=torch.int64, device=dev)
+                h = h.index_select(0, idx)
+                if dropout_masks is not None:
+                    dropout_masks = torch.as_tensor(dropout_masks).reshape(S, 2, B, 256)[:, :, act]
+                if seeds is not None:
+                    seeds = seeds[idx.to(seeds.device)] if torch.is_tensor(seeds) else [seeds[b] for b in act]
+            st_act = _lib.DevLengths([steps[b] for b in act], device=dev)
+            h = self._lstm('_rnn_overlay')(h, lengths=st_act)
+            mel, stats['launches'] = self._ar_decode_batch(h, st_act, seeds, dropout_masks, max_rows, members)
+            stats['rows'], stats['mel_ar'] = act, mel       # (the AR output [len(rows), S * pframes, 80] before the PostNet: parity tests)
+            fr_act = _lib.DevLengths([n * pf for n in st_act], device=dev)
+            out = self._postnet(mel, add_residual=True, lengths=fr_act, channel_major=channel_major)
+            if len(act) < B:
+                full = torch.zeros((B,) + tuple(out.shape[1:]), dtype=out.dtype, device=dev)
+                full[idx] = out
+                out = full
+            _lib.check_split_status('CubenetTextcoder.inference_batch')
+        return (out, frames, stats) if return_stats else (out, frames)
 
     def _ar_decode_stepwise(self, h, dropout_masks=None):
         """The same loop as one kernel launch per layer and step (kept for A/B tests of the persistent kernel)."""
