@@ -675,6 +675,31 @@ int ttsc_expand_rows(const float* x_dev, const int32_t* f2p_dev, const int32_t* 
 int ttsc_cond_input(const float* g_dev, const int32_t* f2p_dev, const int32_t* flen_dev, const float* pitch_out_dev, float max_pitch, int32_t B, int32_t N,
                     int32_t C, int32_t Cp, int32_t Fcap, int32_t F, float* pitch_dev, float* out_dev, void* stream);
 
+/* Prosody control inside those two launches (csrc/prosody.hip).  Under the identity controls both give their uncontrolled twin's
+ * outputs bit for bit; a call without controls uses the twins themselves.
+ * ttsc_align_durations_ctl: ttsc_align_durations with, per phone, dur_scale_q16_dev int32 [B,N] (duration multiplier in Q16, 65536 = unchanged;
+ *   NULL = 65536 everywhere) and dur_set_dev int32 [B,N] (-1 = none, >= 0 = exactly that many frames; NULL = none), and dcap = the largest frame
+ *   count of one phone.  With d = the argmax, per row over p < len[b] in order, in integers:
+ *     acc = 0 (int64, Q16); emitted = 0
+ *     set[p] >= 0: nd = min(set[p], dcap); emitted += nd; acc = emitted << 16
+ *     d == 0:      nd = 0
+ *     else:        acc += d * scale[p]; nd = ((acc + 32768) >> 16) - emitted; nd = min(max(nd, 1), dcap); emitted += nd
+ *   durs[b,p] = nd; f2p and flen = min(emitted, Fcap) as ttsc_align_durations writes them.  The rounding error is carried, so the row's total
+ *   follows the requested tempo; a phone that had frames keeps at least one.
+ * ttsc_cond_input_ctl: ttsc_cond_input with pitch_mul_dev float [B,N] (per phone) and pitch_range_dev float [B] (per row).  A voiced frame
+ *   (vuv == 1) with p0 = (o0 * max_pitch) * vuv becomes, every operation rounded on its own in float32,
+ *     1. pitch_range[b] != 1 and the row has a voiced frame f < flen[b]:  p = m + pitch_range[b] * (p0 - m)
+ *     2. p = p * pitch_mul[b, row(f)];  p = min(max(p, 0), max_pitch)
+ *   m = float32(sum / count) of p0 over the row's voiced frames f < flen[b], summed in float64: lane t of 64 adds frames t, t + 64, ... in that
+ *   order, the 64 partial sums are folded pairwise (part[t] += part[t + off], off = 32 .. 1).  The mean is formed inside the same launch by the
+ *   workgroups that need it: no launch is added, and a row's result does not depend on the rest of the batch.  Unvoiced frames stay 0. */
+int ttsc_align_durations_ctl(const float* logits_dev, const int32_t* len_dev, int32_t B, int32_t N, int32_t D, int32_t* durs_dev,
+                             int32_t* f2p_dev, int32_t* flen_dev, int32_t Fcap, const int32_t* dur_scale_q16_dev, const int32_t* dur_set_dev,
+                             int32_t dcap, void* stream);
+int ttsc_cond_input_ctl(const float* g_dev, const int32_t* f2p_dev, const int32_t* flen_dev, const float* pitch_out_dev, float max_pitch, int32_t B,
+                        int32_t N, int32_t C, int32_t Cp, int32_t Fcap, int32_t F, float* pitch_dev, float* out_dev, const float* pitch_mul_dev,
+                        const float* pitch_range_dev, void* stream);
+
 /* STFT-magnitude / mel-spectrogram helpers around ttsc_linear_forward (the DFT and the mel projection are GEMMs):
  * hifigan.meldataset.mel_spectrogram [EXTERNAL; cube/networks/cubegan.py:137-138,247-248 — the 45 x mel-L1 loss of the GAN step,
  * forward and backward] and MelVocoder.melspectrogram (cube/io_utils/vocoder.py:54-98, feature extraction, row f4).

@@ -24,6 +24,10 @@ def main(argv=None):
     p.add_argument('--output', required=True, help='out.wav (int16, 24 kHz)')
     p.add_argument('--meta', help='out.json: the timestamp list')
     p.add_argument('--device', default='cuda:0')
+    p.add_argument('--rate', type=float, default=1.0, help='speaking rate, > 1 is faster (duration scale 1 / rate, limited to [0.25, 4])')
+    p.add_argument('--pitch', type=float, default=0.0, help='pitch shift in semitones (moves the pitch input of the conditioning recurrence)')
+    p.add_argument('--pitch-range', dest='pitch_range', type=float, default=1.0, help="factor on the spread of the pitch around each paragraph's voiced mean")
+    p.add_argument('--markup', action='store_true', help='paragraphs carry <prosody ..> / <break time=..> tags (ttscube_amd/io_utils/prosody.py)')
     p.add_argument('--max-batch', dest='max_batch', type=int, default=16, help='paragraphs per padded batch (default=16)')
     params = p.parse_args(argv)
     if (params.model is None) == (params.model_path is None):
@@ -41,7 +45,7 @@ def main(argv=None):
     story = StoryCube(params.model, cube=cube, music=params.music, device=params.device, max_batch=params.max_batch)
     with open(params.text_file, encoding='utf-8') as f:
         text = f.read()
-    result = story(text, speaker=params.speaker)
+    result = story(text, speaker=params.speaker, rate=params.rate, pitch=params.pitch, pitch_range=params.pitch_range, markup=params.markup)
     save_wav(params.output, result['audio'], 24000)
     if params.meta:
         with open(params.meta, 'w') as f:

@@ -27,6 +27,62 @@ from .io_utils.io_cubegan import CubeganCollate, CubeganEncodings
 from .networks.cubegan import Cubegan
 
 
+def _per_text(v, n, name):
+    """a call-level control: a scalar for every text, or one value per text"""
+    if isinstance(v, (list, tuple, np.ndarray)):
+        if len(v) != n:
+            raise ValueError('%s: %d values for %d texts' % (name, len(v), n))
+        return list(v)
+    return [v] * n
+
+
+def _plan_prosody(texts, rate, pitch, pitch_range, markup):
+    """What the prosody arguments ask for.  None: nothing — no markup, every control at its identity —, the caller stays on the
+    uncontrolled path.  Else (units, layout): units = [(text index, segment index, tag-free text, spans)], one batch row each (the segments of
+    a text between its <break>s; a text without markup is one unit whose single span is the call-level Prosody); layout[i] = what text i is
+    joined from, in order: ('unit', u) / ('pause', samples)."""
+    from .io_utils.prosody import Prosody, Segment, parse_markup
+    n = len(texts)
+    rates, pitches, ranges, marks = (_per_text(v, n, k) for v, k in ((rate, 'rate'), (pitch, 'pitch'), (pitch_range, 'pitch_range'), (markup, 'markup')))
+    bases = [Prosody(r, p, g) for r, p, g in zip(rates, pitches, ranges)]
+    if not any(marks) and all(b.is_identity() for b in bases):
+        return None
+    units, layout = [], []
+    for i, (text, base, mk) in enumerate(zip(texts, bases, marks)):
+        segs = parse_markup(text, base) if mk else [Segment(text, [(0, len(text), base)])]
+        parts = []
+        for j, seg in enumerate(segs):
+            if len(segs) == 1 or seg.text.strip():          # (a segment without text — two breaks in a row — takes no batch row)
+                parts.append(('unit', len(units)))
+                units.append((i, j, seg.text, seg.spans))
+            if seg.pause_samples() > 0:
+                parts.append(('pause', seg.pause_samples()))
+        layout.append(parts)
+    return units, layout
+
+
+def _join_units(layout, waves, device):
+    """per text: its units' float32 device waveforms with the pauses' zero samples between them, joined on the device"""
+    out = []
+    for parts in layout:
+        ws = [waves[v] if kind == 'unit' else torch.zeros(v, dtype=torch.float32, device=device) for kind, v in parts]
+        out.append(ws[0] if len(ws) == 1 else (torch.cat([w.reshape(-1) for w in ws]) if ws else torch.zeros(0, dtype=torch.float32, device=device)))
+    return out
+
+
+def _control_rows(metas, texts, spans, n_phones):
+    """the per-phone control arrays of one padded batch, in its row order: (dur_scale float64 [B, N], pitch_mul float32 [B, N], pitch_range
+    float32 [B]); padding phones carry the identity"""
+    from .io_utils.prosody import phone_controls
+    B = len(metas)
+    ds, pm, pr = np.ones((B, n_phones), np.float64), np.ones((B, n_phones), np.float32), np.ones((B,), np.float32)
+    for b, (meta, text, sp) in enumerate(zip(metas, texts, spans)):
+        c = phone_controls(meta, text, sp)
+        k = len(c['dur_scale'])
+        ds[b, :k], pm[b, :k], pr[b] = c['dur_scale'], c['pitch_mul'], c['pitch_range']
+    return ds, pm, pr
+
+
 class PhoneText2Feat:
     """Fallback front-end: 'text' is a whitespace-separated phoneme string; '|' separates words."""
 
@@ -122,13 +178,42 @@ class TTSCube:
         rez['meta']['frame2phon'] = [0] * 100
         return rez
 
-    def __call__(self, text, speaker='none'):
-        """cube/api.py:45-66: one sentence -> int16 audio at 24 kHz."""
+    def _attach_controls(self, X, metas, texts, spans):
+        """the control tensors of one collated batch, built behind the collate in its row order (host tensors: Languasito2.inference converts and
+        uploads them); a control that is at its identity in every row is left out, so that such a batch runs the uncontrolled launches"""
+        ds, pm, pr = _control_rows(metas, texts, spans, X['x_char'].shape[1])
+        if (ds != 1.0).any():
+            X['x_dur_scale'] = torch.from_numpy(ds)
+        if (pm != 1.0).any():
+            X['x_pitch_mul'] = torch.from_numpy(pm)
+        if (pr != 1.0).any():
+            X['x_pitch_range'] = torch.from_numpy(pr)
+
+    def __call__(self, text, speaker='none', rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
+        """cube/api.py:45-66: one sentence -> int16 audio at 24 kHz.
+        rate (> 1 is faster; the duration scale 1 / rate is limited to [0.25, 4]), pitch (semitones), pitch_range (factor on the spread of the
+        pitch around the sentence's voiced mean) and markup=True (`text` carries <prosody> / <break> tags: io_utils/prosody.py; the call-level
+        values are then the outermost span) steer the duration and pitch launches of the model.  The pitch controls move the
+        pitch INPUT of the conditioning recurrence; how closely the audio's F0 follows is a property of the trained model."""
+        plan = _plan_prosody([text], rate, pitch, pitch_range, markup)
+        if plan is None:
+            return self._single(text, speaker)
+        units, layout = plan
+        if layout[0] == [('unit', 0)]:
+            return self._single(units[0][2], speaker, units[0][3])
+        wav = self._synthesize_batch_device([text], speaker, 64, rate, pitch, pitch_range, markup)[0]
+        return np.asarray(wav.cpu().numpy() * 32767, dtype=np.int16)
+
+    def _single(self, text, speaker, spans=None):
+        """one sentence (or one segment of a marked-up one) on the single-sentence path; spans: its prosody spans, None = uncontrolled"""
         with torch.no_grad():
-            X = self._collate.collate_fn([self._example(text, speaker)])
+            ex = self._example(text, speaker)
+            X = self._collate.collate_fn([ex])
             for key in X:
                 if isinstance(X[key], torch.Tensor):
                     X[key] = X[key].to(self._model.get_device())
+            if spans is not None:
+                self._attach_controls(X, [ex['meta']], [text], [spans])
             # the generator's range guard runs deferred: nothing waits for the GPU until the audio is copied back — where a synchronisation happens
             # anyway — and the guard's verdict is collected right behind that copy; a tripped guard reruns the sentence with the self-repairing
             # synchronous check (re-calibration on this input)
@@ -146,11 +231,16 @@ class TTSCube:
                 host = self._model.inference(X, check='sync').detach().cpu()
             return np.asarray(host.numpy().squeeze() * 32767, dtype=np.int16)
 
-    def synthesize_batch(self, texts, speaker='none', max_batch=64):
+    def synthesize_batch(self, texts, speaker='none', max_batch=64, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
         """Many sentences -> list of int16 arrays (same order).  Sentences are sorted by phoneme count and run in
         padded batches of up to `max_batch`; ragged lengths are handled inside the kernels (masked BiLSTMs), so each
         result equals the single-sentence call — with word conditioning too: the collate's word counts (x_words_len) stop the word BiLSTMs at each
-        sentence's own last word."""
+        sentence's own last word.
+        rate / pitch / pitch_range / markup: as in `__call__`, each a scalar or one value per text; the segments of every marked-up text go
+        through the same length-sorted groups as rows of their own, and entry i still equals the single call with text i's arguments."""
+        if _plan_prosody(texts, rate, pitch, pitch_range, markup) is not None:
+            return [np.asarray(w.cpu().numpy() * 32767, dtype=np.int16)
+                    for w in self._synthesize_batch_device(texts, speaker, max_batch, rate, pitch, pitch_range, markup)]
         out = [None] * len(texts)
 
         def collect(ids, wav, lens):
@@ -161,10 +251,24 @@ class TTSCube:
         self._run_groups(texts, speaker, max_batch, collect)
         return out
 
-    def _synthesize_batch_device(self, texts, speaker='none', max_batch=64):
+    def _synthesize_batch_device(self, texts, speaker='none', max_batch=64, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
         """`synthesize_batch` without the copy to the host: -> list of 1-D float32 device tensors in (-1, 1), in input order, each trimmed to its
-        own sample count (views of the padded batches).  `np.asarray(t.cpu().numpy() * 32767, dtype=np.int16)` of an entry is that sentence's
-        `synthesize_batch` result.  For callers that go on working on the device (story.StoryCube)."""
+        own sample count (views of the padded batches; with <break>s the segments and their zero samples joined on the device).
+        `np.asarray(t.cpu().numpy() * 32767, dtype=np.int16)` of an entry is that sentence's `synthesize_batch` result.  For callers that go on
+        working on the device (story.StoryCube)."""
+        plan = _plan_prosody(texts, rate, pitch, pitch_range, markup)
+        if plan is not None:
+            units, layout = plan
+            speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
+            waves = [None] * len(units)
+
+            def collect_units(ids, wav, lens):
+                wav = wav.detach()
+                for j, u in enumerate(ids):
+                    waves[u] = wav[j, 0, :lens[j]]
+
+            self._run_groups([u[2] for u in units], [speakers[u[0]] for u in units], max_batch, collect_units, spans=[u[3] for u in units])
+            return _join_units(layout, waves, self._model.get_device())
         out = [None] * len(texts)
 
         def collect(ids, wav, lens):
@@ -175,9 +279,11 @@ class TTSCube:
         self._run_groups(texts, speaker, max_batch, collect)
         return out
 
-    def _run_groups(self, texts, speaker, max_batch, collect):
+    def _run_groups(self, texts, speaker, max_batch, collect, spans=None):
         """the grouping and the inference behind synthesize_batch: `collect(ids, wav [B, 1, L] on the device, sample counts)` is called once per
-        padded batch, ids = the positions of its sentences in `texts`; after a tripped range guard it is called again for every batch."""
+        padded batch, ids = the positions of its sentences in `texts`; after a tripped range guard it is called again for every batch.
+        spans: per text, its prosody spans (io_utils/prosody.py) — the control tensors of a batch are attached behind its collate, so the
+        controls of batch k + 1 travel with its text stack through the pipeline."""
         speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
         # a front-end with a `batch` method (io_text.Text2FeatBlizzard) phonemizes the whole list in one padded call
         feats = self._text2feat.batch(list(texts)) if hasattr(self._text2feat, 'batch') else [None] * len(texts)
@@ -191,6 +297,8 @@ class TTSCube:
                 for key in X:
                     if isinstance(X[key], torch.Tensor):
                         X[key] = X[key].to(self._model.get_device())
+                if spans is not None:
+                    self._attach_controls(X, [ex[i]['meta'] for i in ids], [texts[i] for i in ids], [spans[i] for i in ids])
                 yield X
 
         def collect_all(results):
@@ -332,38 +440,76 @@ class TTSCubeTwoStage:
     def _int16(wav):
         return np.asarray(wav.detach().cpu().numpy().reshape(-1) * 32767, dtype=np.int16)
 
-    def __call__(self, text, speaker='none', seed=None):
-        """one sentence -> int16 audio at the yaml's sample rate; `seed`: the key of the PreNet's dropout masks (None: drawn from torch's generator)"""
+    SEGMENT_KEY_STRIDE = 0x9E3779B97F4A7C15      # (odd: distinct segments of a text never share a key)
+
+    @classmethod
+    def _segment_key(cls, key, j):
+        """the Philox key of segment j (between <break>s) of a text whose key is `key`: (key + j * 0x9E3779B97F4A7C15) mod 2**63 — segment 0, and
+        so every text without a break, keeps `key` itself"""
+        return (int(key) + int(j) * cls.SEGMENT_KEY_STRIDE) % (2 ** 63)
+
+    @staticmethod
+    def _refuse_pitch(pitch, pitch_range):
+        vals = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v]
+        if any(float(v) != 0.0 for v in vals(pitch)) or any(float(v) != 1.0 for v in vals(pitch_range)):
+            raise ValueError('TTSCubeTwoStage: the Textcoder has no pitch input at inference, so pitch / pitch_range cannot be applied; rate and '
+                             '<break> are supported')
+
+    def __call__(self, text, speaker='none', seed=None, rate=1.0, markup=False, pitch=0.0, pitch_range=1.0):
+        """one sentence -> int16 audio at the yaml's sample rate; `seed`: the key of the PreNet's dropout masks (None: drawn from torch's generator).
+        rate / markup: as TTSCube.__call__ (durations and breaks only: a pitch argument, or a pitch / range attribute in the markup, raises
+        ValueError — this model has no pitch input at inference)"""
+        self._refuse_pitch(pitch, pitch_range)
+        if _plan_prosody([text], rate, 0.0, 1.0, markup) is not None:
+            return self._int16(self._synthesize_batch_device([text], speaker, 32, self._seed(seed), rate=rate, markup=markup)[0])
         with torch.no_grad():
             phones = self._phones(text)
             if not phones:                      # (nothing to say: no batch row is made of it)
                 return np.zeros(0, dtype=np.int16)
             return self._int16(self._run(self._collate([phones], [speaker]), [self._seed(seed)])[0])
 
-    def synthesize_batch(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None):
+    def synthesize_batch(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None, rate=1.0, markup=False, pitch=0.0,
+                         pitch_range=1.0):
         """Many sentences -> list of int16 arrays (same order).  Sentences are sorted by phone count and run in padded batches of up to `max_batch`;
         sentence i gets key seed + i, so entry i equals `self(texts[i], seed=seed + i)` whatever the grouping.  members / max_rows: the AR launch
-        shape (CubenetTextcoder._ar_decode_batch) — the defaults keep the single call's bits."""
-        return [self._int16(w) for w in self._synthesize_batch_device(texts, speaker, max_batch, seed, members, max_rows)]
+        shape (CubenetTextcoder._ar_decode_batch) — the defaults keep the single call's bits.  rate / markup: a scalar or one value per text;
+        segment j of a marked-up text is a row of its own with key `_segment_key(seed + i, j)`."""
+        self._refuse_pitch(pitch, pitch_range)
+        return [self._int16(w) for w in self._synthesize_batch_device(texts, speaker, max_batch, seed, members, max_rows, rate, markup)]
 
-    def _synthesize_batch_device(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None):
+    def _synthesize_batch_device(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None, rate=1.0, markup=False):
         """`synthesize_batch` without the copy to the host: list of 1-D float32 device tensors in [-1, 1], input order, each trimmed to its own samples"""
         texts = list(texts)
         speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
         seed = self._seed(seed)
-        feats = self._text2feat.batch(texts) if hasattr(self._text2feat, 'batch') else [None] * len(texts)
-        phones = [self._phones(t, f) for t, f in zip(texts, feats)]
-        order = sorted((i for i in range(len(texts)) if phones[i]), key=lambda i: len(phones[i]))
-        out = [torch.zeros(0, dtype=torch.float32, device=self._device) for _ in texts]      # (a sentence without a phone stays empty and takes no row)
+        plan = _plan_prosody(texts, rate, 0.0, 1.0, markup)
+        if plan is None:
+            units, layout = [(i, 0, t, None) for i, t in enumerate(texts)], [[('unit', i)] for i in range(len(texts))]
+        else:
+            units, layout = plan
+            from .io_utils.prosody import Segment, markup_has_pitch
+            if markup_has_pitch([Segment(u[2], u[3]) for u in units]):
+                raise ValueError('TTSCubeTwoStage: the markup asks for a pitch or a range, and the Textcoder has no pitch input at inference; '
+                                 'rate and <break> are supported')
+        utexts = [u[2] for u in units]
+        feats = self._text2feat.batch(utexts) if hasattr(self._text2feat, 'batch') else [self._text2feat(t) for t in utexts]
+        phones = [list(f['phones']) for f in feats]
+        keys = [self._segment_key(seed + u[0], u[1]) if u[1] else seed + u[0] for u in units]
+        order = sorted((k for k in range(len(units)) if phones[k]), key=lambda k: len(phones[k]))
+        out = [torch.zeros(0, dtype=torch.float32, device=self._device) for _ in units]      # (a sentence without a phone stays empty and takes no row)
         stats = {'launches': 0, 'max_steps': 0}
         with torch.no_grad():
             for s in range(0, len(order), max(1, int(max_batch))):
                 ids = order[s:s + max(1, int(max_batch))]
-                X = self._collate([phones[i] for i in ids], [speakers[i] for i in ids])
-                for i, w in zip(ids, self._run(X, [seed + i for i in ids], members, max_rows)):
-                    out[i] = w
+                X = self._collate([phones[k] for k in ids], [speakers[units[k][0]] for k in ids])
+                if plan is not None:
+                    ds, _, _ = _control_rows([feats[k] for k in ids], [utexts[k] for k in ids], [units[k][3] for k in ids], X['x_char'].shape[1])
+                    if (ds != 1.0).any():
+                        X['x_dur_scale'] = torch.from_numpy(ds)
+                for k, w in zip(ids, self._run(X, [keys[k] for k in ids], members, max_rows)):
+                    out[k] = w
                 stats = {'launches': stats['launches'] + self.last_stats['launches'], 'max_steps': max(stats['max_steps'], self.last_stats['max_steps'])}
         self.last_stats = stats
-        return out
+        return out if plan is None else _join_units(layout, out, self._device)
 
     shard = staticmethod(TTSCube.shard)

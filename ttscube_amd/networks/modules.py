@@ -403,12 +403,67 @@ def _char_lengths(X, x_char):
     return ((x_char != 0).long() * pos).max(dim=1).values.tolist()
 
 
-def align_durations(out_dur, lengths):
+from ..io_utils.prosody import DUR_SCALE_MAX, DUR_SCALE_MIN     # (the accepted range of a duration multiplier: Prosody limits 1 / rate to it)
+
+
+def _control(v, shape, name):
+    """a per-phone / per-row control of X as a host numpy array of `shape` (a device tensor is read back: controls are host data to begin with)"""
+    a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError('%s: shape %s, expected %s' % (name, tuple(a.shape), tuple(shape)))
+    return a
+
+
+def dur_scale_q16(scale):
+    """duration multipliers (floats in [0.25, 4]) -> int32 Q16, round to nearest on the host"""
+    a = np.asarray(scale, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError('x_dur_scale: not finite')
+    q = np.rint(a * 65536.0).astype(np.int64)
+    lo, hi = int(round(DUR_SCALE_MIN * 65536)), int(round(DUR_SCALE_MAX * 65536))
+    if q.size and (q.min() < lo or q.max() > hi):
+        raise ValueError('x_dur_scale: duration multipliers must lie in [%g, %g] (got %g .. %g)' % (DUR_SCALE_MIN, DUR_SCALE_MAX, q.min() / 65536.0, q.max() / 65536.0))
+    return q.astype(np.int32)
+
+
+def _align_durations_ctl(out_dur, lengths, dur_scale, dur_set, dcap):
+    """the controlled launch (csrc/prosody.hip::ttsc_align_durations_ctl): same outputs as align_durations, Fcap = N * dcap"""
+    B, N, D = out_dur.shape
+    dev = out_dur.device
+    q = dur_scale_q16(_control(dur_scale, (B, N), 'x_dur_scale')) if dur_scale is not None else None
+    st = _control(dur_set, (B, N), 'x_dur_set').astype(np.int64) if dur_set is not None else None
+    if dcap is None:
+        dcap = -(-(D - 1) * (int(q.max()) if q is not None and q.size else 65536) // 65536)
+        if st is not None and st.size:
+            dcap = max(dcap, int(st.max()))
+    dcap = int(dcap)
+    if dcap < 0 or N * max(dcap, 1) >= 2 ** 31 or (st is not None and st.size and st.max() >= 2 ** 31):
+        raise ValueError('align_durations: dcap = %d does not fit a frame map of %d phones' % (dcap, N))
+    fcap = max(1, N * dcap)
+    durs = torch.empty((B, N), dtype=torch.int32, device=dev)
+    f2p = torch.empty((B, fcap), dtype=torch.int32, device=dev)
+    flen = torch.empty((B,), dtype=torch.int32, device=dev)
+    len_t = _lib.lengths_dev(lengths, dev)
+    q_t = torch.from_numpy(q).to(dev) if q is not None else None
+    st_t = torch.from_numpy(np.maximum(st, -1).astype(np.int32)).to(dev) if st is not None else None
+    P = lambda t: _lib.dev_ptr(t) if t is not None else None
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().ttsc_align_durations_ctl(_lib.dev_ptr(out_dur), P(len_t), B, N, D, _lib.dev_ptr(durs), _lib.dev_ptr(f2p), _lib.dev_ptr(flen),
+                                                       fcap, P(q_t), P(st_t), dcap, _lib.current_stream()), 'ttsc_align_durations_ctl')
+    return Alignment(f2p, flen, _lib.DevLengths(flen.cpu().tolist(), dev_tensor=flen), durs)
+
+
+def align_durations(out_dur, lengths, dur_scale=None, dur_set=None, dcap=None):
     """argmax over the duration head [B, N, D], exclusive scan and scatter of phone indices, all in one kernel; the host
-    reads back B frame counts (it needs them to size the expanded tensors) and nothing else."""
+    reads back B frame counts (it needs them to size the expanded tensors) and nothing else.
+    dur_scale (float [B, N] in [0.25, 4]) / dur_set (int [B, N], -1 = none, >= 0 = exactly that many frames) / dcap (the largest
+    frame count of one phone; default ceil((D - 1) * max scale), at least the largest dur_set): with any of them the controlled kernel runs
+    instead — still one launch — and the frame map holds N * dcap entries per row.  Without them this is the uncontrolled launch, untouched."""
     out_dur = out_dur.float().contiguous()
     B, N, D = out_dur.shape
     dev = out_dur.device
+    if dur_scale is not None or dur_set is not None or dcap is not None:
+        return _align_durations_ctl(out_dur, lengths, dur_scale, dur_set, dcap)
     fcap = max(1, N * (D - 1))
     durs = torch.empty((B, N), dtype=torch.int32, device=dev)
     f2p = torch.empty((B, fcap), dtype=torch.int32, device=dev)
@@ -565,7 +620,10 @@ class Languasito2(nn.Module):
         (zero rows beyond each utterance's own frame count); X['y_frame2phone'] / X['y_pitch'] are (re)written like
         the reference does.  `timers` (optional list): (phase name, HIP event) pairs are appended at the phase boundaries
         ('text' = phoneme-level stacks + duration head, 'alignment' = durations -> frame map + row expansion, 'frames' = frame-level
-        stacks) — bench.py --mode e2e reports them."""
+        stacks) — bench.py --mode e2e reports them.
+        Prosody controls (optional entries of X, host data): 'x_dur_scale' float [B,N] in [0.25, 4] (duration multiplier per phone),
+        'x_dur_set' int [B,N] (-1 = none, >= 0 = exactly that many frames), 'x_pitch_mul' float [B,N] and 'x_pitch_range' float [B] (factor on
+        the pitch INPUT of the conditioning recurrence, per phone / spread around the row's voiced mean).  Without them nothing changes."""
         def mark(name):
             if timers is not None:
                 ev = torch.cuda.Event(enable_timing=True)
@@ -608,7 +666,7 @@ class Languasito2(nn.Module):
                 g_char.record_stream(cur_s)
             mark('text')
             # duration head -> frame->phone map on the device (the reference goes through the host here, modules.py:946-953)
-            f2p = align_durations(out_dur, lengths)
+            f2p = align_durations(out_dur, lengths, X.get('x_dur_scale'), X.get('x_dur_set'))   # (controls, when X carries them: same launch count)
             X['y_frame2phone'] = f2p
             hexp, flens = _expand_rows(hcs, f2p)
             mark('alignment')
@@ -624,7 +682,30 @@ class Languasito2(nn.Module):
                 g = g_char
             else:
                 g = self._text_stack('g', x_char, x_speaker, lengths, X, hf_cond)
-            if COND_INPUT_FUSED and op.is_cuda:
+            pitch_ctl = X.get('x_pitch_mul') is not None or X.get('x_pitch_range') is not None
+            if pitch_ctl:
+                # pitch controls live in the fused launch and nowhere else (whatever TTSC_COND_INPUT_FUSED says): per-phone multiplier, per-row range
+                # around the row's own voiced mean — formed inside the same launch (csrc/prosody.hip::ttsc_cond_input_ctl)
+                g = g.float().contiguous()
+                Cg = g.shape[2]
+                Cp = (Cg + 1 + 3) // 4 * 4
+                pm, pr = X.get('x_pitch_mul'), X.get('x_pitch_range')
+                pm = np.ones((B, N), np.float32) if pm is None else _control(pm, (B, N), 'x_pitch_mul').astype(np.float32)
+                pr = np.ones((B,), np.float32) if pr is None else _control(pr, (B,), 'x_pitch_range').astype(np.float32)
+                if not (np.all(np.isfinite(pm)) and np.all(np.isfinite(pr)) and (pm >= 0).all() and (pr >= 0).all()):
+                    raise ValueError('x_pitch_mul / x_pitch_range: finite, non-negative factors expected')
+                pm_t, pr_t = torch.from_numpy(pm).to(dev), torch.from_numpy(pr).to(dev)
+                pitch = torch.empty((B, F_), dtype=torch.float32, device=dev)
+                gin = torch.empty((B, F_, Cp), dtype=torch.float32, device=dev)
+                opc = op.float().contiguous()
+                with _lib.on_device(dev):
+                    _lib.check(_lib.lib().ttsc_cond_input_ctl(_lib.dev_ptr(g), _lib.dev_ptr(f2p.f2p), _lib.dev_ptr(f2p.flen_dev), _lib.dev_ptr(opc),
+                                                              float(self._max_pitch), B, g.shape[1], Cg, Cp, f2p.f2p.shape[1], F_, _lib.dev_ptr(pitch),
+                                                              _lib.dev_ptr(gin), _lib.dev_ptr(pm_t), _lib.dev_ptr(pr_t), _lib.current_stream()),
+                               'ttsc_cond_input_ctl')
+                X['y_pitch'] = pitch
+                g = gin
+            elif COND_INPUT_FUSED and op.is_cuda:
                 # voiced flag, pitch, row expansion, the pitch feature and the split GEMM's zero columns in ONE launch (ttsc_cond_input: nine elementwise
                 # launches of ~9 us each on the critical path of a sentence otherwise); per element the operations of the lines below
                 g = g.float().contiguous()

@@ -67,6 +67,14 @@ class CubenetTextcoder(nn.Module):
         hd = self._lstm('_dur_rnn')(h, lengths=lengths)
         return h, linear_hip(hd, self._dur_output.linear_layer.weight, self._dur_output.linear_layer.bias)
 
+    @staticmethod
+    def _dur_controls(X):
+        """the duration controls of X ('x_dur_scale' float [B, N] in [0.25, 4], 'x_dur_set' int [B, N]: Languasito2.inference's, DESIGN.md §9n);
+        this model takes no pitch input at inference, so a pitch control is refused instead of being dropped"""
+        if X.get('x_pitch_mul') is not None or X.get('x_pitch_range') is not None:
+            raise ValueError('CubenetTextcoder has no pitch input at inference: x_pitch_mul / x_pitch_range cannot be applied (duration controls only)')
+        return X.get('x_dur_scale'), X.get('x_dur_set')
+
     def inference(self, X, dropout_masks=None, seed=None):
         """textcoder.py:140-189 (B=1 like the reference; `inference_batch` takes a padded batch).  dropout_masks: optional [steps, 2, 1, 256]
         {0,1} PreNet masks (parity tests); otherwise drawn in the kernel from Philox with key `seed` (None: a key from torch's generator).
@@ -77,7 +85,7 @@ class CubenetTextcoder(nn.Module):
         with torch.no_grad():
             h, out_dur = self._text_stack(x_char, x_speaker, None)
             # duration head -> alignment -> gathered overlay input, all on the device (textcoder.py:160-166,291-302 do it on the host)
-            h, _ = _expand_rows(h, align_durations(out_dur, None), stride=self._pframes)
+            h, _ = _expand_rows(h, align_durations(out_dur, None, *self._dur_controls(X)), stride=self._pframes)
             if h.shape[1] == 0:
                 return torch.zeros((1, 0, 80), device=dev)
             h = self._lstm('_rnn_overlay')(h)
@@ -227,7 +235,7 @@ class CubenetTextcoder(nn.Module):
         with torch.no_grad():
             lengths = _lib.DevLengths(_char_lengths(X, x_char), device=dev)
             h, out_dur = self._text_stack(x_char, x_speaker, lengths)
-            h, steps = _expand_rows(h, align_durations(out_dur, lengths), stride=pf)
+            h, steps = _expand_rows(h, align_durations(out_dur, lengths, *self._dur_controls(X)), stride=pf)
             steps = [int(v) for v in steps]
             frames = [n * pf for n in steps]
             S = max(steps) if steps else 0
