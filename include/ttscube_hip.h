@@ -532,6 +532,27 @@ int ttsc_colsum(const float* x_dev, int64_t R, int64_t C, int64_t ld, float* out
  * nominal peak (csrc/probe.hip).  Synchronises `stream`.  No counterpart in the reference (it has no kernels). */
 int ttsc_probe_mfma_tflops(int32_t mode, double ms_target, double* tflops_out, void* stream);
 
+/* Test-only probes of include/ttscube_math.h (csrc/probe.hip, compiled with the library's ordinary flags): the device evaluates the shared
+ * definitions element by element so that tests/test_shared_math_gpu.py can hold them equal, bit for bit, to the host build of the same header
+ * (oracle/wavernn_ref.c: wr_math_array, wr_philox_array, wr_noise_array, wr_sample_array — same fn / kind numbering).  All asynchronous on
+ * `stream`.  No counterpart in the reference. */
+enum {
+    TTSC_PROBE_EXPF = 0, TTSC_PROBE_LOGF = 1, TTSC_PROBE_SIGMOIDF = 2, TTSC_PROBE_TANHF = 3, TTSC_PROBE_NORMAL_ICDF = 4, TTSC_PROBE_LOGISTIC = 5,
+    TTSC_PROBE_U01 = 6, TTSC_PROBE_U01_CLIP = 7, TTSC_PROBE_GUMBEL = 8   /* 6 - 8 read the input as uint32 */
+};
+/* out_dev[i] = fn(in_dev[i]), one thread per element; in_dev: n floats (fn <= 5) or n uint32 (fn >= 6) */
+int ttsc_probe_math(int32_t fn, const void* in_dev, float* out_dev, int64_t n, void* stream);
+/* out_dev[i, 0:4] = ttsc_philox4x32(counter ctr_dev[i, 0:4], key key_dev[i, 0:2]) */
+int ttsc_probe_philox(const uint32_t* ctr_dev, const uint32_t* key_dev, uint32_t* out_dev, int64_t n, void* stream);
+/* out_dev[i, 0:W] = ttsc_noise_mol / _gm / _beta (t_dev[i], b_dev[i], seed_dev[i]); kind = TTSC_WR_OUT_MOL / GM / BETA, W = 11 / 1 / 18 */
+int ttsc_probe_noise(int32_t kind, const uint32_t* t_dev, const uint32_t* b_dev, const uint64_t* seed_dev, float* out_dev, int64_t n, void* stream);
+/* One continuous sample per row of y_dev [n, S] (S = 30 MOL, 2 GM / BETA): wv_dev[i] the sample, k_dev[i] the mixture index (0 unless MOL).
+ * mode = TTSC_WR_MODE_*: ARGMAX zero noise, NOISE noise_dev [n, W], PHILOX counters (t_dev[i], b_dev[i]) under key seed_dev[i] (unused
+ * pointers may be NULL).  impl 0: ttsc_sample_mol / _gm / _beta of the header, one thread per row; impl 1: the decode kernels' wave-parallel
+ * wr_sample_continuous (csrc/wavernn_sampler.hpp), one wave per row. */
+int ttsc_probe_sample(int32_t out_kind, int32_t mode, int32_t impl, const float* y_dev, const float* noise_dev, const uint32_t* t_dev,
+                      const uint32_t* b_dev, const uint64_t* seed_dev, float* wv_dev, int32_t* k_dev, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LSTM / BiLSTM recurrence.  Replaces the sequential part of torch.nn.LSTM (gate order i,f,g,o, `_reverse`
  * direction) for Languasito2 (modules.py:873-905) and CubenetTextcoder (textcoder.py:55-92).

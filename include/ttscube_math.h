@@ -6,8 +6,42 @@
  * device and on the host.  libm (glibc) and the ROCm device library round differently, so these are
  * written with nothing but IEEE-754 correctly-rounded operations (fmaf, +, *, /, rintf) and integer bit
  * moves, which gcc (-ffp-contract=off) and hipcc (gfx950, correctly-rounded division is hipcc's default)
- * evaluate identically.  Accuracy: expf <= 1 ulp-ish (rel 1.2e-7), logf rel 2e-7; they are pinned against
- * torch's fp32 results in tests/test_oracle_wavernn.py within 1e-6.
+ * evaluate identically.  That is tested function by function: tests/test_shared_math_gpu.py evaluates every function below on the
+ * device (csrc/probe.hip) over every 1021st bit pattern plus the neighbourhoods of every branch point and holds the bits equal to the
+ * host build's (NaN for NaN, payload not compared).
+ *
+ * Accuracy of the host build against float64 on those inputs (tests/test_shared_math_cpu.py asserts exactly these figures: the measured
+ * maxima rounded up to two digits; the same table stands in DESIGN.md).  Claims: expf rel <= 1.2e-7, logf rel <= 2e-7, sigmoid / tanh
+ * abs <= 2^-23 (ACT_ABS of the recurrence tests), icdf abs <= 5e-4 — all hold.
+ *
+ *   function          | domain                                  | max ulp | max rel | max abs | worst argument (ulp; rel; abs)
+ *   ttsc_expf         | finite |x| <= 87                        | 0.90    | 7.5e-8  | 2.6e30  | 48.177822; same; 86.99198
+ *   ttsc_logf         | normal positive floats                  | 2.7     | 2.0e-7  | 3.9e-6  | 1.0284861; 1.3003923; 1.155e35
+ *   ttsc_sigmoidf     | finite |x| <= 87                        | 2.1     | 1.4e-7  | 8.9e-8  | -16.657656; -16.85629; 7.4648695
+ *   ttsc_tanhf        | all finite x                            | 27      | 1.7e-6  | 1.1e-7  | 0.06250017; -0.06260858; 0.078903265
+ *   ttsc_normal_icdf  | p = ttsc_u01(r)                         | 2300    | 1.4e-4  | 2.7e-4  | 0.024462402 (just above plow), all three
+ *   ttsc_gumbel       | r (u = ttsc_u01(r))                     | 1.5e7   | 1.0     | 5.4e-7  | r = 1580030172 (u = 1/e: the result is 0); abs: r = 4293914537
+ *   ttsc_gumbel_clip  | -logf(-logf(u)), u = ttsc_u01_clip(r)   | 1.5e7   | 1.0     | 5.7e-7  | u = 0.36787945; abs: u = 0.9997061 (the Gumbel terms of ttsc_noise_mol)
+ *   ttsc_logistic     | u = ttsc_u01(r) and ttsc_u01_clip(r)    | 1100    | 1.2e-4  | 9.4e-7  | 0.49987406 (the result crosses 0); abs: 0.00032562017
+ *
+ * tanh loses its relative accuracy just above the branch at |x| = 2^-4 (cancellation in 1 - 2/(e+1)), the Gumbel and logistic terms where
+ * their result crosses zero: for these the absolute figure is the meaningful one, which is why ACT_ABS is an absolute bound.
+ * ttsc_u01 is exact (23 bits + one half); ttsc_u01_clip is one fmaf and stays inside [1e-5f, 1 - 1e-5f].
+ *
+ * Outside the domains the contract is only that both sides return the same bits; tests/test_shared_math_cpu.py pins the values as they are:
+ *   - ttsc_expf clamps: expf(x <= -87, -inf) = expf(-87) = 1.6458115e-38, expf(x >= 88, +inf) = expf(88) = 1.6516363e38.
+ *   - ttsc_sigmoidf is subnormal below x = -87.34 and never 0: sigmoid(x <= -88) = 6.054601e-39; sigmoid(+inf) = 1.
+ *   - ttsc_tanhf(+-inf) = +-1; ttsc_tanhf(-0.0f) = +0 (the sign is taken from x < 0).
+ *   - NaN in gives NaN out for expf, sigmoidf, tanhf and normal_icdf.
+ *   - ttsc_logf reads the exponent and mantissa fields (the sign bit counts as exponent bit 8) and never tests the class: finite garbage for
+ *     0 (-88.02969), subnormals (1e-40f: -88.02122), negative numbers (-2: 178.13882), +inf (88.72284) and NaN (89.1283); hence
+ *     ttsc_logistic(NaN) = 0 on the host and ttsc_normal_icdf(0) = -13.003056, ttsc_normal_icdf(1) = 13.003056.
+ *   - DOMAIN LIMIT, the one input class on which host and device differ: ttsc_logf of a NaN that an arithmetic operation PRODUCED.  IEEE 754
+ *     does not fix the sign or payload of such a NaN (x86 keeps the operand's sign in 1.0f - NaN, gfx950 flips it), and ttsc_logf turns those
+ *     bits into a number.  Hence ttsc_logistic(u) requires u not NaN (host 0 or -0.405, device +-177.4: both pinned in
+ *     tests/test_shared_math_gpu.py::test_logistic_of_nan_is_outside_the_contract), and the noise scalars handed to ttsc_gamma_mt
+ *     (logf(1.0f - nz[..])) must not be NaN.  No caller reaches this: the uniforms come from ttsc_u01 / ttsc_u01_clip, which never leave
+ *     (0, 1), and injected noise is finite.
  *
  * Every function is `static inline`; in HIP translation units they are __host__ __device__.
  */

@@ -315,3 +315,85 @@ void wr_noise_beta(uint32_t t, uint32_t b, uint64_t seed, float* nz) { ttsc_nois
 void wr_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
     ttsc_philox4x32(c0, c1, c2, c3, k0, k1, out);
 }
+
+/* ---- array entries: the host side of the device probes (ttsc_probe_* of include/ttscube_hip.h, same fn / kind numbering) ----
+ * One call per sweep instead of one ctypes call per value (tests/test_shared_math_cpu.py, tests/test_shared_math_gpu.py). */
+enum { FN_EXPF = 0, FN_LOGF = 1, FN_SIGMOIDF = 2, FN_TANHF = 3, FN_NORMAL_ICDF = 4, FN_LOGISTIC = 5, FN_U01 = 6, FN_U01_CLIP = 7, FN_GUMBEL = 8 };
+
+/* out[i] = fn(in[i]); in: n floats (fn <= 5) or n uint32 (fn >= 6) */
+int wr_math_array(int fn, const void* in, float* out, int64_t n) {
+    const float* x = (const float*)in;
+    const uint32_t* r = (const uint32_t*)in;
+    if (fn < FN_EXPF || fn > FN_GUMBEL) return -1;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+        float y;
+        switch (fn) {
+            case FN_EXPF: y = ttsc_expf(x[i]); break;
+            case FN_LOGF: y = ttsc_logf(x[i]); break;
+            case FN_SIGMOIDF: y = ttsc_sigmoidf(x[i]); break;
+            case FN_TANHF: y = ttsc_tanhf(x[i]); break;
+            case FN_NORMAL_ICDF: y = ttsc_normal_icdf(x[i]); break;
+            case FN_LOGISTIC: y = ttsc_logistic(x[i]); break;
+            case FN_U01: y = ttsc_u01(r[i]); break;
+            case FN_U01_CLIP: y = ttsc_u01_clip(r[i]); break;
+            default: y = ttsc_gumbel(r[i]); break;
+        }
+        out[i] = y;
+    }
+    return 0;
+}
+
+/* out[i, 0:4] = philox4x32(counter ctr[i, 0:4], key key[i, 0:2]) */
+void wr_philox_array(const uint32_t* ctr, const uint32_t* key, uint32_t* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) ttsc_philox4x32(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], key[2 * i], key[2 * i + 1], out + 4 * i);
+}
+
+static int noise_width_of(int out_kind) { return out_kind == OUT_MOL ? TTSC_MOL_NOISE : out_kind == OUT_GM ? TTSC_GM_NOISE : TTSC_BETA_NOISE; }
+
+static void noise_of(int out_kind, uint32_t t, uint32_t b, uint64_t seed, float* nz) {
+    if (out_kind == OUT_MOL) ttsc_noise_mol(t, b, seed, nz);
+    else if (out_kind == OUT_GM) ttsc_noise_gm(t, b, seed, nz);
+    else ttsc_noise_beta(t, b, seed, nz);
+}
+
+/* out[i, 0:W] = ttsc_noise_mol / _gm / _beta (t[i], b[i], seed[i]); kind = OUT_MOL / OUT_GM / OUT_BETA, W = 11 / 1 / 18 */
+int wr_noise_array(int kind, const uint32_t* t, const uint32_t* b, const uint64_t* seed, float* out, int64_t n) {
+    if (kind != OUT_MOL && kind != OUT_GM && kind != OUT_BETA) return -1;
+    const int w = noise_width_of(kind);
+    for (int64_t i = 0; i < n; ++i) {
+        float nz[TTSC_BETA_NOISE];
+        noise_of(kind, t[i], b[i], seed[i], nz);
+        memcpy(out + i * w, nz, sizeof(float) * w);
+    }
+    return 0;
+}
+
+/* one continuous sample per row of y [n, S] through the header's samplers, with the noise set up as in wr_decode_at: wv[i] the sample,
+ * k[i] the mixture index (0 unless MOL).  mode: MODE_ARGMAX zero noise, MODE_NOISE noise [n, W], MODE_PHILOX (t[i], b[i], seed[i]). */
+int wr_sample_array(int out_kind, int mode, const float* y, const float* noise, const uint32_t* t, const uint32_t* b, const uint64_t* seed,
+                    float* wv, int32_t* k, int64_t n) {
+    if (out_kind != OUT_MOL && out_kind != OUT_GM && out_kind != OUT_BETA) return -1;
+    if (mode < MODE_ARGMAX || mode > MODE_PHILOX) return -1;
+    const int S = out_kind == OUT_MOL ? 3 * TTSC_MOL_NMIX : 2, w = noise_width_of(out_kind);
+    for (int64_t i = 0; i < n; ++i) {
+        float nz[TTSC_BETA_NOISE];
+        for (int j = 0; j < TTSC_BETA_NOISE; ++j) nz[j] = 0.f;
+        if (mode == MODE_NOISE) {
+            memcpy(nz, noise + i * w, sizeof(float) * w);
+        } else if (mode == MODE_PHILOX) {
+            noise_of(out_kind, t[i], b[i], seed[i], nz);
+        } else if (out_kind == OUT_BETA) {
+            for (int v = 0; v < 2; ++v) nz[v * (1 + 2 * TTSC_BETA_TRIES)] = 0.5f, nz[v * (1 + 2 * TTSC_BETA_TRIES) + 2] = 0.5f;
+        }
+        int best = 0;
+        if (out_kind == OUT_MOL)
+            wv[i] = ttsc_sample_mol(y + i * S, nz, nz[TTSC_MOL_NMIX], &best);
+        else if (out_kind == OUT_GM)
+            wv[i] = ttsc_sample_gm(y + i * S, nz[0]);
+        else
+            wv[i] = ttsc_sample_beta(y + i * S, nz);
+        k[i] = best;
+    }
+    return 0;
+}

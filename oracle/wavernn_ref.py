@@ -52,7 +52,72 @@ def lib():
         _lib.wr_sample_mol.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.wr_noise_beta.restype = None
         _lib.wr_noise_beta.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]
+        _lib.wr_math_array.restype = C.c_int
+        _lib.wr_math_array.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+        _lib.wr_philox_array.restype = None
+        _lib.wr_philox_array.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        _lib.wr_noise_array.restype = C.c_int
+        _lib.wr_noise_array.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int64]
+        _lib.wr_sample_array.restype = C.c_int
+        _lib.wr_sample_array.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64]
     return _lib
+
+
+# ---- array entries: the host side of the device probes (ttsc_probe_* of include/ttscube_hip.h), same numbering ----
+FN_EXPF, FN_LOGF, FN_SIGMOIDF, FN_TANHF, FN_NORMAL_ICDF, FN_LOGISTIC, FN_U01, FN_U01_CLIP, FN_GUMBEL = range(9)
+FN_NAMES = ('expf', 'logf', 'sigmoidf', 'tanhf', 'normal_icdf', 'logistic', 'u01', 'u01_clip', 'gumbel')
+
+
+def _arr(a, dtype):
+    return np.ascontiguousarray(np.asarray(a, dtype=dtype))
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def math_array(fn, x):
+    """fn(x) of include/ttscube_math.h, host build, elementwise: x float32 (fn <= FN_LOGISTIC) or uint32 (fn >= FN_U01) -> float32"""
+    x = _arr(x, np.uint32 if fn >= FN_U01 else np.float32)
+    out = np.empty(x.shape, dtype=np.float32)
+    assert lib().wr_math_array(fn, _p(x), _p(out), x.size) == 0
+    return out
+
+
+def philox_array(ctr, key):
+    """ctr [n, 4], key [n, 2] uint32 -> [n, 4] uint32"""
+    ctr, key = _arr(ctr, np.uint32), _arr(key, np.uint32)
+    assert ctr.ndim == 2 and ctr.shape[1] == 4 and key.shape == (ctr.shape[0], 2)
+    out = np.empty_like(ctr)
+    lib().wr_philox_array(_p(ctr), _p(key), _p(out), ctr.shape[0])
+    return out
+
+
+def noise_array(kind, t, b, seed):
+    """ttsc_noise_mol / _gm / _beta at (t[i], b[i], seed[i]); kind 'mol' | 'gm' | 'beta' -> [n, NOISE_WIDTH[kind]] float32"""
+    t, b, seed = _arr(t, np.uint32), _arr(b, np.uint32), _arr(seed, np.uint64)
+    assert t.shape == b.shape == seed.shape and t.ndim == 1
+    out = np.empty((t.size, NOISE_WIDTH[kind]), dtype=np.float32)
+    assert lib().wr_noise_array(OUT_KIND[kind], _p(t), _p(b), _p(seed), _p(out), t.size) == 0
+    return out
+
+
+def sample_array(kind, mode, y, noise=None, t=None, b=None, seed=None):
+    """the header's continuous samplers on the rows of y [n, SAMPLE_SIZE[kind]] -> (wv [n] float32, k [n] int32)"""
+    y = _arr(y, np.float32)
+    n = y.shape[0]
+    assert y.shape == (n, SAMPLE_SIZE[kind])
+    if mode == MODE_NOISE:
+        noise = _arr(noise, np.float32)
+        assert noise.shape == (n, NOISE_WIDTH[kind])
+    if mode == MODE_PHILOX:
+        t, b, seed = _arr(t, np.uint32), _arr(b, np.uint32), _arr(seed, np.uint64)
+        assert t.shape == b.shape == seed.shape == (n,)
+    wv, k = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+    rc = lib().wr_sample_array(OUT_KIND[kind], mode, _p(y), _p(noise) if mode == MODE_NOISE else None,
+                               *([_p(t), _p(b), _p(seed)] if mode == MODE_PHILOX else [None] * 3), _p(wv), _p(k), n)
+    assert rc == 0
+    return wv, k
 
 
 def mulaw_lut(golden_dir=None):
