@@ -500,7 +500,9 @@ void ttsc_wavernn_destroy(ttsc_wavernn* w);
 int ttsc_linear_forward(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int64_t M, int32_t N,
                         int32_t K, int64_t ldx, int64_t ldy, int32_t act, int32_t accumulate, void* stream);
 /* The same contract on the f16 matrix pipe with fp32-class accuracy (gemm.hip: gemm_nt_f16x3_kernel): operands split into fp16 hi / lo halves on
- * their way into LDS, three MFMA products per tile (lo.hi + hi.lo + hi.hi, fp32 accumulation) — ~2^-22 relative per product.  Operands must lie
+ * their way into LDS, three MFMA products per tile (lo.hi + hi.lo + hi.hi, fp32 accumulation).  The low half is stored scaled by 2^11 and its two
+ * products are accumulated apart (added as acc_hi + 2^-11 acc_lo), so the accuracy does not depend on the operands' scale: ~2^-22 relative per
+ * product, per element within 2^-20 of sum |x||w| for operand magnitudes 2^-14 .. 65504 (below 2^-14 a value keeps an absolute 2^-36).  Operands must lie
  * inside the fp16 range (|v| <= 65504): anything beyond sets a sticky per-device status word, read (and cleared; synchronises) by
  * ttsc_gemm_split_status — 1 = a result since the last call is invalid.  lengths_dev [M / period] or NULL: rows are [utterance][period]; 128-row
  * tiles that lie wholly at or beyond their utterances' lengths are skipped and stay unwritten (the recurrences never read them).
@@ -516,6 +518,8 @@ int32_t ttsc_gemm_split_status(void);
  *     C[M, :N] (+)= opA(A) . opB(B)     transA = 0: A is [M,K] (lda), 1: A is [K,M];   transB = 0: B is [K,N] (ldb), 1: B is [N,K]
  *   dx = dG . W (NN), dW = dG^T . x (TN), dW_hh = dG^T . h_prev (TN with b_row_shift = -1 / +1 and b_period = T: row r of the
  *   contraction reads B row r + shift when 0 <= r % period + shift < period and zero otherwise, so h_prev is never materialised).
+ *   A non-zero shift needs |shift| < b_period and K % b_period == 0 (whole sequences: with a partial last period a forward shift would
+ *   read B row K); anything else is TTSC_EINVAL before any launch.
  * When M x N tiles alone cannot fill the device the contraction is split over K; partial tiles go through ws_dev
  * (>= ttsc_gemm_workspace_bytes(M, N, K); may be NULL when that is 0) and are added in a fixed order (deterministic).
  * ttsc_colsum: out[c] (+)= sum_r x[r, c] (bias gradients), two fixed-order stages through ws_dev (>= ttsc_colsum_workspace_bytes). */

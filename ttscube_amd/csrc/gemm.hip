@@ -118,16 +118,37 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The same NT contract on the f16 matrix pipe with fp32-class accuracy: every fp32 operand value v is split on its way into LDS into
-// hi = rn16(v), lo = rn16(v - hi) and the product is summed as lo_x.hi_w + hi_x.lo_w + hi_x.hi_w in fp32 accumulators (three
-// v_mfma_f32_32x32x16_f16 per tile and 16 k: the ceiling is a third of the dense f16 peak = 833 TFLOP/s against 157 for the fp32 MFMA above).
-// The dropped lo.lo term and the two roundings leave ~2^-22 relative per product — the split the vocoder convolutions use (conv1d.hip), here
-// without pre-scales: operands must lie inside the fp16 range (|v| <= 65504; anything beyond sets the launch's status word, reported by
-// ttsc_gemm_split_status) and values below 2^-14 keep only an absolute 2^-25.  Callers: the hoisted input projections of the text-side
-// BiLSTMs (activations of tanh / LSTM layers, embeddings, mel frames).  `lengths` / `period`: rows are [utterance][period] and rows at or
-// beyond an utterance's length are padding nobody reads — a 128-row tile that lies wholly in padding returns at once (its outputs stay
-// unwritten).  128 x 128 x 32 tile, 4 waves as 2 x 2, each 2 x 2 MFMA tiles; the next k-slice's global loads are in flight during the MFMAs.
+// hi = rn16(v), lo' = rn16((v - hi) * 2^11) and the product is summed as hi_x.hi_w in one set of fp32 accumulators and lo'_x.hi_w + hi_x.lo'_w
+// in a second one; the epilogue adds them as acc_hi + 2^-11 * acc_lo (three v_mfma_f32_32x32x16_f16 per tile and 16 k: the ceiling is a third
+// of the dense f16 peak = 833 TFLOP/s against 157 for the fp32 MFMA above).  Why the low half is scaled: |v - hi| <= 2^-11 |v|, so an unscaled
+// low half is an fp16 subnormal — absolute 2^-25, whatever |v| — as soon as |v| < 2^-3, and the result degrades with the operand scale
+// (2^-18 of sum |x||w| at weights of 2^-9, 2^-14 at 2^-13; conv1d.hip carries power-of-two pre-scales for the same reason).  Scaled by
+// 2^11 the low half has the magnitude of v's last hi bit (<= 2^15: no overflow) and stays a normal fp16 down to |v| = 2^-14; below that
+// it keeps an absolute 2^-36.  The dropped lo.lo term and the roundings leave ~2^-22 relative per product for 2^-14 <= |v| <= 65504 —
+// measured per element against float64: 2^-23.2 .. 2^-22.3 of sum |x||w| for operand scales 2^-14 .. 2^10, 2^-20.9 where one or two products
+// carry the whole sum (tests/test_gemm_f64_gpu.py holds 2^-20 everywhere).
+// Operands must lie inside the fp16 range (|v| <= 65504; anything beyond sets the launch's status word, reported by ttsc_gemm_split_status).
+// Callers: the hoisted input projections of the text-side BiLSTMs (activations of tanh / LSTM layers, embeddings, mel frames).  `lengths` /
+// `period`: rows are [utterance][period] and rows at or beyond an utterance's length are padding nobody reads — a 128-row tile that lies
+// wholly in padding returns at once (its outputs stay unwritten).  128 x 128 x 32 tile, 4 waves as 2 x 2, each 2 x 2 MFMA tiles; the next
+// k-slice's global loads are in flight during the MFMAs.
 typedef _Float16 gemm_half8 __attribute__((ext_vector_type(8)));
 constexpr int SK = 32, SLD = SK + 8;   // k-slice, LDS row pitch in halfs (80 bytes: 16-byte aligned fragments)
+constexpr float GEMM_LO_SCALE = 2048.f, GEMM_LO_UNSCALE = 1.f / 2048.f;   // 2^11: one fp16 significand
+
+// split2_f16 (conv_internal.hpp) with the low half scaled: hi = rn16(v), lo' = rn16((v - hi) * 2^11).  v - hi is exact (v_fma_mix_f32, as
+// there) and so is the power of two; local to this file — the convolutions' split keeps its bits.
+__device__ __forceinline__ void gemm_split2_f16(float v0, float v1, unsigned& hi, unsigned& lo) {
+    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+    typedef float f2_t __attribute__((ext_vector_type(2)));
+    const f2_t p = {v0, v1};
+    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(p, h2_t));
+    float l0, l1;
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hi), "v"(v0));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hi), "v"(v1));
+    const f2_t l = {l0 * GEMM_LO_SCALE, l1 * GEMM_LO_SCALE};
+    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(l, h2_t));
+}
 
 struct GemmSplitArgs {
     const float* X;
@@ -141,7 +162,9 @@ struct GemmSplitArgs {
     unsigned* status;
 };
 
-__global__ __launch_bounds__(256) void gemm_nt_f16x3_kernel(GemmSplitArgs a) {
+// (two waves per SIMD: 128 accumulator + ~120 other registers fit the 256 of that occupancy unspilled; without the bound the compiler
+// takes 270 and the occupancy halves)
+__global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmSplitArgs a) {
     __shared__ __attribute__((aligned(16))) _Float16 Ah[GM * SLD];
     __shared__ __attribute__((aligned(16))) _Float16 Al[GM * SLD];
     __shared__ __attribute__((aligned(16))) _Float16 Bh[GN * SLD];
@@ -158,13 +181,13 @@ __global__ __launch_bounds__(256) void gemm_nt_f16x3_kernel(GemmSplitArgs a) {
         }
         if (!__syncthreads_or(live)) return;
     }
-    f32x16 acc[2][2];
+    f32x16 acc[2][2], acl[2][2];   // hi.hi, and the two cross products at 2^11 times their weight
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = acl[i][j][r] = 0.f;
     float4 ra[4], rb[4];
     unsigned bad = 0;
     // 128 rows x 8 float4 per operand and k-slice -> 4 per thread and operand; 8 consecutive lanes read one row's 128 bytes
@@ -181,8 +204,8 @@ __global__ __launch_bounds__(256) void gemm_nt_f16x3_kernel(GemmSplitArgs a) {
     };
     auto put = [&](const float4& v, _Float16* hi_plane, _Float16* lo_plane, int off) {
         unsigned h0, l0, h1, l1;
-        split2_f16(v.x, v.y, h0, l0);
-        split2_f16(v.z, v.w, h1, l1);
+        gemm_split2_f16(v.x, v.y, h0, l0);
+        gemm_split2_f16(v.z, v.w, h1, l1);
         // a hi half with an all-ones exponent: the value was beyond the fp16 range (or not finite)
         bad |= (unsigned)(((h0 & 0x7c00u) == 0x7c00u) | ((h0 & 0x7c000000u) == 0x7c000000u) | ((h1 & 0x7c00u) == 0x7c00u) | ((h1 & 0x7c000000u) == 0x7c000000u));
         *reinterpret_cast<uint2*>(hi_plane + off) = make_uint2(h0, h1);
@@ -218,11 +241,11 @@ __global__ __launch_bounds__(256) void gemm_nt_f16x3_kernel(GemmSplitArgs a) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acl[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acl[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acl[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acl[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -242,7 +265,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f16x3_kernel(GemmSplitArgs a) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (m < a.M) {
                     float* y = a.Y + (size_t)m * a.ldy + n;
-                    float v = acc[i][j][r] + bv;
+                    float v = (acc[i][j][r] + GEMM_LO_UNSCALE * acl[i][j][r]) + bv;
                     if (a.accumulate) v += *y;
                     *y = gemm_act(v, a.act);
                 }
@@ -546,6 +569,9 @@ extern "C" int ttsc_gemm(int32_t transA, int32_t transB, int64_t M, int64_t N, i
                  "ttsc_gemm: leading dimensions too small (lda=%lld ldb=%lld ldc=%lld)", (long long)lda, (long long)ldb, (long long)ldc);
     TTSC_REQUIRE(b_row_shift == 0 || (!transB && b_period > 0 && b_row_shift > -b_period && b_row_shift < b_period),
                  "ttsc_gemm: the row shift applies to an untransposed B ([K, N]) with a positive period");
+    // a last, partial period: row K - 1 would pass the in-period test under a forward shift and read B row K (past the operand)
+    TTSC_REQUIRE(b_row_shift == 0 || K % b_period == 0, "ttsc_gemm: a row shift needs whole periods (K=%lld is no multiple of b_period=%lld)",
+                 (long long)K, (long long)b_period);
     const int splits = gemm_splits(M, N, K);
     TTSC_REQUIRE(splits == 1 || (ws_dev && ws_bytes >= (size_t)splits * M * N * sizeof(float)), "ttsc_gemm: workspace too small (need %zu bytes)",
                  (size_t)splits * M * N * sizeof(float));

@@ -127,7 +127,8 @@ SPLIT_GEMM = os.environ.get('TTSC_GEMM_SPLIT', '1') != '0'
 def linear_hip(x, weight, bias=None, act=None, out=None, accumulate=False, split=False, lengths_dev=None, period=0):
     """y[..., :N] = act(x[..., :K] @ weight[N,K]^T + bias) on the MFMA GEMM (ttsc_linear_forward).
     x: device tensor [..., K] (last dim contiguous, rows at a constant stride); weight/bias: device tensors.
-    split: run on the f16 matrix pipe with fp32-class accuracy (ttsc_linear_forward_split: hi / lo fp16 halves, three products — operands
+    split: run on the f16 matrix pipe with fp32-class accuracy (ttsc_linear_forward_split: hi / lo fp16 halves, the low half scaled by 2^11,
+    three products — per element within 2^-20 of sum |x||w| for operand magnitudes 2^-14 .. 65504, whatever the operands' scale; operands
     must lie inside the fp16 range, checked on the device and reported by _lib.check_split_status); shapes the split kernel does not take
     run on the exact fp32 kernel.  lengths_dev (int32 device tensor [B]) with period = T for x [B, T, K]: rows t >= lengths[b] are padding
     nobody reads — whole row tiles of padding are skipped and stay UNWRITTEN (split kernel only)."""
@@ -167,7 +168,7 @@ def gemm_hip(a, b, trans_a=False, trans_b=False, out=None, accumulate=False, b_r
     """out[M, N] (+)= op(a) @ op(b) on the fp32 MFMA GEMM (ttsc_gemm): a is [M, K] ([K, M] when trans_a), b is [K, N] ([N, K] when
     trans_b); 2-D device tensors whose last dimension is contiguous (row strides are passed as leading dimensions, so column slices
     of a wider tensor work without a copy).  b_row_shift / b_period: see include/ttscube_hip.h (h_prev of a recurrence without
-    materialising it).  Deterministic (split-K partials are added in a fixed order)."""
+    materialising it; K must be whole periods).  Deterministic (split-K partials are added in a fixed order)."""
     for t in (a, b):
         if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
             raise _lib.TTSCError('gemm_hip: operands must be 2-D fp32 device tensors with a contiguous last dimension')
@@ -175,6 +176,9 @@ def gemm_hip(a, b, trans_a=False, trans_b=False, out=None, accumulate=False, b_r
     N, Kb = (b.shape[0], b.shape[1]) if trans_b else (b.shape[1], b.shape[0])
     if Kb != K:
         raise _lib.TTSCError('gemm_hip: contraction lengths differ (%d vs %d)' % (K, Kb))
+    if b_row_shift and (trans_b or b_period <= 0 or abs(b_row_shift) >= b_period or K % b_period):
+        raise _lib.TTSCError('gemm_hip: a row shift needs an untransposed b, |shift| < b_period and K a multiple of b_period '
+                             '(shift %d, period %d, K %d)' % (b_row_shift, b_period, K))
     if out is None:
         if accumulate:
             raise _lib.TTSCError('gemm_hip: accumulate=True needs an `out` tensor')
