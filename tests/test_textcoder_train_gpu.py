@@ -1,7 +1,8 @@
 """GPU: CubenetTextcoder training (networks/textcoder_train.py, csrc/textcoder_train.hip).
 
   * the BatchNorm -> tanh -> dropout kernels against float64 torch (outputs / running statistics <= 1e-5, gradients <= 1e-4 relative, bit-identical
-    repeats), and the Philox mask path;
+    repeats), and the Philox mask path — the per-element statement of these kernels and of the loss (every dispatch path, |got - ref64| <=
+    tau * S with no absolute floor) is tests/test_text_train_f64_gpu.py;
   * the loss kernel against float64 torch (ignored rows, ignore_index >= classes, an all-ignored head) and its out-of-range status;
   * reference parity (tests/golden/textcoder_train_{a,b,pf1}.npz, made by the reference itself): outputs, losses, every gradient and the running
     statistics after a step, every parameter after two Adam steps — the gate of the Languasito2 training parity test (1e-4 relative);
