@@ -1048,6 +1048,40 @@ int ttsc_segment_gather(const int16_t* wav_arena_dev, const int64_t* wav_off_dev
                         const int64_t* mel_off_dev, const int32_t* utt_dev, const int32_t* start_frame_dev, int32_t B, int32_t n_mels,
                         int32_t frames, int32_t hop, float mel_scale, float mel_pad, float* y_out_dev, float* mel_out_dev, void* stream);
 
+/* Loudness meter and gain stage (csrc/loudness.hip; io_utils/loudness.py; the float64 statement is tests/loudness_reference.py): ITU-R BS.1770-4
+ * integrated loudness of mono rows at any rate sr that is a positive multiple of 10 with sr / 10 >= 64, a 4x true peak, one static gain per row.
+ *   x [B, Lmax] float32, len [B] int32 (clamped to [0, Lmax]); samples behind a row's length are never read.  1 <= B <= 65535, Lmax < 2^31.
+ * ttsc_loudness_measure:
+ *   kweight_host  154 float64 ON THE HOST: b0 b1 b2 a1 a2 of the shelf, the same of the high-pass (transposed direct form II, a0 = 1), then nine
+ *                 row-major 4x4 matrices A^(64 2^k), k = 0 .. 8, A being one step of the cascade's state at zero input (io_utils/loudness.py)
+ *   taps_host     84 float32 ON THE HOST: [4][21], entry [p][d + 10] = fl32(h[4 d + p + 40]) of the 81-tap 4x filter h, 0 where outside
+ *   sub [B, nsub_max] float64, nsub_max >= ceil(Lmax / (sr / 10)): sum of squares of the K-weighted row over samples [k sr/10, (k+1) sr/10) and
+ *                 [0, len); 0 behind the row.  float64 state and sums in one fixed order: a row has the same bits alone and in any batch
+ *   sample_peak, true_peak [B] float32: max |x|, and max |y| of the row oversampled 4x with h (zeros outside the row; the 4x signal is not stored)
+ *   workspace     ttsc_loudness_workspace_bytes(B, Lmax, sr) bytes, 8-byte aligned
+ * ttsc_loudness_finish (one workgroup per row): blocks z_j = (sub[j] + .. + sub[j+3]) / (4 sr/10) over whole sub-blocks, or ONE block, the mean
+ *   square of the whole row, for 0 < len < 4 sr/10; none for len = 0.  Strict gates in the energy domain: z_j > abs_gate, then also
+ *   z_j > 0.1 mean(z over the first gate).  zbar [B] float64 = mean z over both gates (0 and silent = 1 when none passes); blocks, gated, silent
+ *   [B] int32.  With gain_dev: gain [B] float32 = fl32(min(sqrt(target_energy[b] / zbar), peak_lin[b] / max(sample peak, true peak),
+ *   max_gain_lin when > 0)), 1 for a silent row; limited [B] int32 (may be NULL) = 1 where the peak ceiling set the gain.  target_energy and
+ *   peak_lin are [B] float64 on the device: 10^((target + 0.691) / 10) and 10^(peak_db / 20).
+ * ttsc_loudness_gain: the gain and limited of ttsc_loudness_finish from stored results, for another target.
+ * ttsc_loudness_apply: y[b, n] = fl32(gain[b] x[b, n]) for n < len[b], nothing is written behind; y may be x; y [B, Lmax] like x.  16-byte
+ *   accesses where a row of x and of y sit alike to a 16-byte boundary, 4-byte accesses otherwise, the same bits.
+ * Every argument is checked before the first launch or memset: a refused call leaves its outputs untouched. */
+size_t ttsc_loudness_workspace_bytes(int32_t B, int64_t Lmax, int32_t sr);
+int ttsc_loudness_measure(const float* x_dev, const int32_t* len_dev, int32_t B, int64_t Lmax, int32_t sr, const double* kweight_host,
+                          const float* taps_host, double* sub_dev, int64_t nsub_max, float* sample_peak_dev, float* true_peak_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+int ttsc_loudness_finish(const double* sub_dev, const int32_t* len_dev, int32_t B, int64_t Lmax, int64_t nsub_max, int32_t sr,
+                         const float* sample_peak_dev, const float* true_peak_dev, double abs_gate, const double* target_energy_dev,
+                         const double* peak_lin_dev, double max_gain_lin, double* zbar_dev, int32_t* blocks_dev, int32_t* gated_dev,
+                         int32_t* silent_dev, float* gain_dev, int32_t* limited_dev, void* stream);
+int ttsc_loudness_gain(const double* zbar_dev, const float* sample_peak_dev, const float* true_peak_dev, const int32_t* silent_dev,
+                       const double* target_energy_dev, const double* peak_lin_dev, double max_gain_lin, int32_t B, float* gain_dev,
+                       int32_t* limited_dev, void* stream);
+int ttsc_loudness_apply(const float* x_dev, const int32_t* len_dev, const float* gain_dev, int32_t B, int64_t Lmax, float* y_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

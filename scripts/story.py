@@ -27,6 +27,8 @@ def main(argv=None):
     p.add_argument('--rate', type=float, default=1.0, help='speaking rate, > 1 is faster (duration scale 1 / rate, limited to [0.25, 4])')
     p.add_argument('--pitch', type=float, default=0.0, help='pitch shift in semitones (moves the pitch input of the conditioning recurrence)')
     p.add_argument('--pitch-range', dest='pitch_range', type=float, default=1.0, help="factor on the spread of the pitch around each paragraph's voiced mean")
+    p.add_argument('--loudness', type=float, default=None, help='bring every paragraph to this integrated loudness in LUFS before the mix (BS.1770-4; '
+                   'default: the level the generator gives)')
     p.add_argument('--markup', action='store_true', help='paragraphs carry <prosody ..> / <break time=..> tags (ttscube_amd/io_utils/prosody.py)')
     p.add_argument('--max-batch', dest='max_batch', type=int, default=16, help='paragraphs per padded batch (default=16)')
     params = p.parse_args(argv)
@@ -45,7 +47,8 @@ def main(argv=None):
     story = StoryCube(params.model, cube=cube, music=params.music, device=params.device, max_batch=params.max_batch)
     with open(params.text_file, encoding='utf-8') as f:
         text = f.read()
-    result = story(text, speaker=params.speaker, rate=params.rate, pitch=params.pitch, pitch_range=params.pitch_range, markup=params.markup)
+    result = story(text, speaker=params.speaker, rate=params.rate, pitch=params.pitch, pitch_range=params.pitch_range, markup=params.markup,
+                   loudness=params.loudness)
     save_wav(params.output, result['audio'], 24000)
     if params.meta:
         with open(params.meta, 'w') as f:

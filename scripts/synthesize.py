@@ -26,6 +26,9 @@ def parser():
     p.add_argument('--seed', type=int, default=0, help='line i is decoded with key seed + i')
     p.add_argument('--device', default='cuda:0')
     p.add_argument('--rate', type=float, default=1.0, help='speaking rate, > 1 is faster (duration scale 1 / rate, limited to [0.25, 4])')
+    p.add_argument('--loudness', type=float, default=None, help='bring every sentence to this integrated loudness in LUFS (BS.1770-4; default: the '
+                   'level the vocoder gives)')
+    p.add_argument('--peak', type=float, default=-1.0, help='true-peak ceiling in dB for --loudness')
     p.add_argument('--markup', action='store_true', help='lines carry <prosody rate=..> / <break time=..> tags (ttscube_amd/io_utils/prosody.py)')
     return p
 
@@ -58,7 +61,8 @@ def main(argv=None):
         vocoder = GriffinLimVocoder(sample_rate=int(conf.get('sample_rate', 24000)), hop_size=int(conf.get('hop_size', 240)), device=params.device)
     tts = TTSCubeTwoStage(params.textcoder, vocoder, phonemizer_path=params.phonemizer, device=params.device)
     os.makedirs(params.output_folder, exist_ok=True)
-    wavs = tts.synthesize_batch(texts, speaker=params.speaker, max_batch=params.batch, seed=params.seed, rate=params.rate, markup=params.markup)
+    wavs = tts.synthesize_batch(texts, speaker=params.speaker, max_batch=params.batch, seed=params.seed, rate=params.rate, markup=params.markup,
+                                loudness=params.loudness, peak_db=params.peak)
     for i, w in enumerate(wavs):
         save_wav(os.path.join(params.output_folder, '%05d.wav' % (i + 1)), w, tts.sample_rate)
     sys.stdout.write('%d files -> %s\n' % (len(wavs), params.output_folder))

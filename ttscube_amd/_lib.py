@@ -294,6 +294,13 @@ SIGNATURES = {
     'ttsc_stft_project': (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
     'ttsc_stft_overlap_add': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'ttsc_segment_gather': (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_float, C.c_float] + [C.c_void_p] * 3),
+    'ttsc_loudness_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
+    'ttsc_loudness_measure': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'ttsc_loudness_finish': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 7),
+    'ttsc_loudness_gain': (C.c_int, [C.c_void_p] * 6 + [C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttsc_loudness_apply': (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 

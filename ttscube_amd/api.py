@@ -70,6 +70,66 @@ def _join_units(layout, waves, device):
     return out
 
 
+def _plan_loudness(loudness, peak_db, n):
+    """loudness=None: None, and nothing of io_utils/loudness.py is imported or launched.  Else (targets, peaks): one LUFS target and one
+    true-peak ceiling in dB per text"""
+    if loudness is None:
+        return None
+    return ([float(v) for v in _per_text(loudness, n, 'loudness')], [float(v) for v in _per_text(peak_db, n, 'peak_db')])
+
+
+def _normalize_padded(wav, lens, ids, plan, sample_rate, log=None):
+    """one padded batch [B, 1, L] of device waveforms, row j being text ids[j] -> the same batch brought to its texts' loudness targets (measure,
+    finish and apply: io_utils/loudness.py, no host synchronisation).  log: a dict that receives, under the batch's ids, its small per-row device
+    results (zbar, gain, limited, silent) — a batch that is run again, after a tripped range guard, replaces its entry"""
+    from .io_utils.loudness import meter
+    B, L = wav.shape[0], wav.shape[-1]
+    if B == 0 or L == 0:
+        return wav
+    x = wav.detach().reshape(B, L).contiguous()
+    ld = torch.tensor([int(v) for v in lens], dtype=torch.int32).pin_memory().to(x.device, non_blocking=True)
+    y, st = meter(x.device).normalize_device(x, ld, sample_rate, [plan[0][i] for i in ids], peak_db=[plan[1][i] for i in ids], inplace=False)
+    if log is not None:
+        log[tuple(ids)] = {k: st[k] for k in ('zbar', 'gain', 'limited', 'silent')}
+    return y.reshape(B, 1, L)
+
+
+def _loudness_report(log, n):
+    """the per-text reports of the last call with a loudness target, read back from the device: [{lufs_in, gain_db, peak_limited, silent}] (None
+    for a text that had no sample)"""
+    import math
+    from .io_utils.loudness import lufs
+    out = [None] * n
+    for ids, st in log.items():
+        z, g = lufs(st['zbar'].cpu().numpy()), st['gain'].cpu().numpy()
+        lim, sil = st['limited'].cpu().numpy(), st['silent'].cpu().numpy()
+        for j, i in enumerate(ids):
+            out[i] = {'lufs_in': float(z[j]), 'gain_db': 20.0 * math.log10(float(g[j])), 'peak_limited': bool(lim[j]), 'silent': bool(sil[j])}
+    return out
+
+
+def _normalize_in_groups(waves, plan, sample_rate, device, max_batch, log=None):
+    """_normalize_waves over the whole list, `max_batch` texts per padded batch"""
+    step = max(1, int(max_batch))
+    out = list(waves)
+    for s in range(0, len(out), step):
+        out[s:s + step] = _normalize_waves(out[s:s + step], plan, sample_rate, device, log, first=s)
+    return out
+
+
+def _normalize_waves(waves, plan, sample_rate, device, log=None, first=0):
+    """a list of 1-D device waveforms (texts first, first + 1, ...: sentences joined from their <break> segments are measured as the joined unit)
+    -> the list at the texts' loudness targets, through one padded batch"""
+    lens = [int(w.numel()) for w in waves]
+    if not lens or max(lens) == 0:
+        return waves
+    x = torch.zeros((len(waves), 1, max(lens)), dtype=torch.float32, device=device)
+    for i, w in enumerate(waves):
+        x[i, 0, :lens[i]] = w.reshape(-1)
+    y = _normalize_padded(x, lens, list(range(first, first + len(waves))), plan, sample_rate, log)
+    return [y[i, 0, :lens[i]] for i in range(len(waves))]
+
+
 def _control_rows(metas, texts, spans, n_phones):
     """the per-phone control arrays of one padded batch, in its row order: (dur_scale float64 [B, N], pitch_mul float32 [B, N], pitch_range
     float32 [B]); padding phones carry the identity"""
@@ -97,6 +157,8 @@ class PhoneText2Feat:
 
 
 class TTSCube:
+    SAMPLE_RATE = 24000
+
     def __init__(self, model_path: str, phonemizer_path: str = None, text2feat=None, device='cuda:0', word_vectors=None):
         encodings = CubeganEncodings('{0}.encodings'.format(model_path))
         conf = yaml.load(open('{0}.yaml'.format(model_path)), yaml.Loader)
@@ -189,12 +251,17 @@ class TTSCube:
         if (pr != 1.0).any():
             X['x_pitch_range'] = torch.from_numpy(pr)
 
-    def __call__(self, text, speaker='none', rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
+    def __call__(self, text, speaker='none', rate=1.0, pitch=0.0, pitch_range=1.0, markup=False, loudness=None, peak_db=-1.0):
         """cube/api.py:45-66: one sentence -> int16 audio at 24 kHz.
+        loudness (LUFS; None: the level the generator gives, nothing new runs) and peak_db (true-peak ceiling in dB): the sentence is brought
+        to that integrated loudness on the device (io_utils/loudness.py) before the int16 conversion.
         rate (> 1 is faster; the duration scale 1 / rate is limited to [0.25, 4]), pitch (semitones), pitch_range (factor on the spread of the
         pitch around the sentence's voiced mean) and markup=True (`text` carries <prosody> / <break> tags: io_utils/prosody.py; the call-level
         values are then the outermost span) steer the duration and pitch launches of the model.  The pitch controls move the
         pitch INPUT of the conditioning recurrence; how closely the audio's F0 follows is a property of the trained model."""
+        if loudness is not None:
+            wav = self._synthesize_batch_device([text], speaker, 64, rate, pitch, pitch_range, markup, loudness, peak_db)[0]
+            return np.asarray(wav.cpu().numpy() * 32767, dtype=np.int16)
         plan = _plan_prosody([text], rate, pitch, pitch_range, markup)
         if plan is None:
             return self._single(text, speaker)
@@ -231,16 +298,17 @@ class TTSCube:
                 host = self._model.inference(X, check='sync').detach().cpu()
             return np.asarray(host.numpy().squeeze() * 32767, dtype=np.int16)
 
-    def synthesize_batch(self, texts, speaker='none', max_batch=64, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
+    def synthesize_batch(self, texts, speaker='none', max_batch=64, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False, loudness=None, peak_db=-1.0):
         """Many sentences -> list of int16 arrays (same order).  Sentences are sorted by phoneme count and run in
         padded batches of up to `max_batch`; ragged lengths are handled inside the kernels (masked BiLSTMs), so each
         result equals the single-sentence call — with word conditioning too: the collate's word counts (x_words_len) stop the word BiLSTMs at each
         sentence's own last word.
         rate / pitch / pitch_range / markup: as in `__call__`, each a scalar or one value per text; the segments of every marked-up text go
-        through the same length-sorted groups as rows of their own, and entry i still equals the single call with text i's arguments."""
-        if _plan_prosody(texts, rate, pitch, pitch_range, markup) is not None:
+        through the same length-sorted groups as rows of their own, and entry i still equals the single call with text i's arguments.
+        loudness / peak_db: as in `__call__`, a scalar or one value per text; measured and scaled on the device, batch by batch."""
+        if loudness is not None or _plan_prosody(texts, rate, pitch, pitch_range, markup) is not None:
             return [np.asarray(w.cpu().numpy() * 32767, dtype=np.int16)
-                    for w in self._synthesize_batch_device(texts, speaker, max_batch, rate, pitch, pitch_range, markup)]
+                    for w in self._synthesize_batch_device(texts, speaker, max_batch, rate, pitch, pitch_range, markup, loudness, peak_db)]
         out = [None] * len(texts)
 
         def collect(ids, wav, lens):
@@ -251,11 +319,16 @@ class TTSCube:
         self._run_groups(texts, speaker, max_batch, collect)
         return out
 
-    def _synthesize_batch_device(self, texts, speaker='none', max_batch=64, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
+    def _synthesize_batch_device(self, texts, speaker='none', max_batch=64, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False, loudness=None,
+                                 peak_db=-1.0):
         """`synthesize_batch` without the copy to the host: -> list of 1-D float32 device tensors in (-1, 1), in input order, each trimmed to its
         own sample count (views of the padded batches; with <break>s the segments and their zero samples joined on the device).
         `np.asarray(t.cpu().numpy() * 32767, dtype=np.int16)` of an entry is that sentence's `synthesize_batch` result.  For callers that go on
-        working on the device (story.StoryCube)."""
+        working on the device (story.StoryCube).  loudness / peak_db: every entry at its loudness target (a sentence without <break>s inside the
+        padded batch it was generated in, one with <break>s as the joined unit)."""
+        loud = _plan_loudness(loudness, peak_db, len(texts))
+        if loud is not None:
+            self._loud_log = (len(texts), {})
         plan = _plan_prosody(texts, rate, pitch, pitch_range, markup)
         if plan is not None:
             units, layout = plan
@@ -268,16 +341,24 @@ class TTSCube:
                     waves[u] = wav[j, 0, :lens[j]]
 
             self._run_groups([u[2] for u in units], [speakers[u[0]] for u in units], max_batch, collect_units, spans=[u[3] for u in units])
-            return _join_units(layout, waves, self._model.get_device())
+            joined = _join_units(layout, waves, self._model.get_device())
+            if loud is None:
+                return joined
+            return _normalize_in_groups(joined, loud, self.SAMPLE_RATE, self._model.get_device(), max_batch, self._loud_log[1])
         out = [None] * len(texts)
 
         def collect(ids, wav, lens):
-            wav = wav.detach()
+            wav = wav.detach() if loud is None else _normalize_padded(wav, lens, ids, loud, self.SAMPLE_RATE, self._loud_log[1])
             for j, i in enumerate(ids):
                 out[i] = wav[j, 0, :lens[j]]
 
         self._run_groups(texts, speaker, max_batch, collect)
         return out
+
+    def loudness_report(self):
+        """per text of the last call that had a loudness target: {lufs_in, gain_db, peak_limited, silent} (this reads the statistics back)"""
+        n, log = getattr(self, '_loud_log', (0, {}))
+        return _loudness_report(log, n)
 
     def _run_groups(self, texts, speaker, max_batch, collect, spans=None):
         """the grouping and the inference behind synthesize_batch: `collect(ids, wav [B, 1, L] on the device, sample counts)` is called once per
@@ -455,13 +536,14 @@ class TTSCubeTwoStage:
             raise ValueError('TTSCubeTwoStage: the Textcoder has no pitch input at inference, so pitch / pitch_range cannot be applied; rate and '
                              '<break> are supported')
 
-    def __call__(self, text, speaker='none', seed=None, rate=1.0, markup=False, pitch=0.0, pitch_range=1.0):
+    def __call__(self, text, speaker='none', seed=None, rate=1.0, markup=False, pitch=0.0, pitch_range=1.0, loudness=None, peak_db=-1.0):
         """one sentence -> int16 audio at the yaml's sample rate; `seed`: the key of the PreNet's dropout masks (None: drawn from torch's generator).
         rate / markup: as TTSCube.__call__ (durations and breaks only: a pitch argument, or a pitch / range attribute in the markup, raises
-        ValueError — this model has no pitch input at inference)"""
+        ValueError — this model has no pitch input at inference).  loudness / peak_db: as TTSCube.__call__"""
         self._refuse_pitch(pitch, pitch_range)
-        if _plan_prosody([text], rate, 0.0, 1.0, markup) is not None:
-            return self._int16(self._synthesize_batch_device([text], speaker, 32, self._seed(seed), rate=rate, markup=markup)[0])
+        if loudness is not None or _plan_prosody([text], rate, 0.0, 1.0, markup) is not None:
+            return self._int16(self._synthesize_batch_device([text], speaker, 32, self._seed(seed), rate=rate, markup=markup, loudness=loudness,
+                                                             peak_db=peak_db)[0])
         with torch.no_grad():
             phones = self._phones(text)
             if not phones:                      # (nothing to say: no batch row is made of it)
@@ -469,17 +551,22 @@ class TTSCubeTwoStage:
             return self._int16(self._run(self._collate([phones], [speaker]), [self._seed(seed)])[0])
 
     def synthesize_batch(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None, rate=1.0, markup=False, pitch=0.0,
-                         pitch_range=1.0):
+                         pitch_range=1.0, loudness=None, peak_db=-1.0):
         """Many sentences -> list of int16 arrays (same order).  Sentences are sorted by phone count and run in padded batches of up to `max_batch`;
         sentence i gets key seed + i, so entry i equals `self(texts[i], seed=seed + i)` whatever the grouping.  members / max_rows: the AR launch
         shape (CubenetTextcoder._ar_decode_batch) — the defaults keep the single call's bits.  rate / markup: a scalar or one value per text;
-        segment j of a marked-up text is a row of its own with key `_segment_key(seed + i, j)`."""
+        segment j of a marked-up text is a row of its own with key `_segment_key(seed + i, j)`.  loudness / peak_db: a scalar or one value per
+        text, measured and scaled on the device."""
         self._refuse_pitch(pitch, pitch_range)
-        return [self._int16(w) for w in self._synthesize_batch_device(texts, speaker, max_batch, seed, members, max_rows, rate, markup)]
+        return [self._int16(w) for w in self._synthesize_batch_device(texts, speaker, max_batch, seed, members, max_rows, rate, markup, loudness,
+                                                                      peak_db)]
 
-    def _synthesize_batch_device(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None, rate=1.0, markup=False):
-        """`synthesize_batch` without the copy to the host: list of 1-D float32 device tensors in [-1, 1], input order, each trimmed to its own samples"""
+    def _synthesize_batch_device(self, texts, speaker='none', max_batch=32, seed=None, members=None, max_rows=None, rate=1.0, markup=False,
+                                 loudness=None, peak_db=-1.0):
+        """`synthesize_batch` without the copy to the host: list of 1-D float32 device tensors in [-1, 1], input order, each trimmed to its own samples.
+        loudness / peak_db: every entry (a text with <break>s as the joined unit) at its loudness target, one padded batch per `max_batch` texts"""
         texts = list(texts)
+        loud = _plan_loudness(loudness, peak_db, len(texts))
         speakers = speaker if isinstance(speaker, (list, tuple)) else [speaker] * len(texts)
         seed = self._seed(seed)
         plan = _plan_prosody(texts, rate, 0.0, 1.0, markup)
@@ -510,6 +597,11 @@ class TTSCubeTwoStage:
                     out[k] = w
                 stats = {'launches': stats['launches'] + self.last_stats['launches'], 'max_steps': max(stats['max_steps'], self.last_stats['max_steps'])}
         self.last_stats = stats
-        return out if plan is None else _join_units(layout, out, self._device)
+        out = out if plan is None else _join_units(layout, out, self._device)
+        if loud is not None:
+            self._loud_log = (len(texts), {})
+            out = _normalize_in_groups(out, loud, self.sample_rate, self._device, max_batch, self._loud_log[1])
+        return out
 
     shard = staticmethod(TTSCube.shard)
+    loudness_report = TTSCube.loudness_report

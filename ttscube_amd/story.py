@@ -52,14 +52,17 @@ class StoryCube:
             raise ValueError('StoryCube: the background music must be a non-empty mono signal, got shape %s' % (tuple(music.shape),))
         return music.to(self._device)
 
-    def __call__(self, text, speaker=None, background_music_path: str = None, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False):
+    def __call__(self, text, speaker=None, background_music_path: str = None, rate=1.0, pitch=0.0, pitch_range=1.0, markup=False, loudness=None,
+                 peak_db=-1.0):
         """-> {'audio': np.int16 [total], 'meta': [...]} with the reference's keys and float values (cube/story.py:13-56).
         rate / pitch / pitch_range / markup: TTSCube.__call__'s prosody controls, applied to every paragraph; with markup=True
-        each paragraph is read as markup on its own (tags do not span paragraphs, and a paragraph may not contain a newline)."""
+        each paragraph is read as markup on its own (tags do not span paragraphs, and a paragraph may not contain a newline).
+        loudness (LUFS, a scalar or one value per paragraph; None: the generator's own level) / peak_db: every paragraph is brought to that
+        integrated loudness on the device before the mix; the music path and `meta` do not change."""
         parts = text.split('\n\n')
         music = self._default_music if background_music_path is None else self._upload_music(background_music_path)
         waves = self._cube._synthesize_batch_device(parts, speaker=speaker, max_batch=self._max_batch, rate=rate, pitch=pitch, pitch_range=pitch_range,
-                                                    markup=markup)
+                                                    markup=markup, **({} if loudness is None else {'loudness': loudness, 'peak_db': peak_db}))
         lengths = [int(w.numel()) for w in waves]
         seg_dst, total, meta = plan_timeline(lengths, SAMPLE_RATE, texts=parts)
         seg_src = [sum(lengths[:p]) for p in range(len(lengths))]
