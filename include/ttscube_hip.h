@@ -128,7 +128,25 @@ int ttsc_conv1d_forward_ragged(const ttsc_conv1d* c, const float* x_dev, int32_t
 int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x_dev, int32_t B, int64_t Lin, float* y_dev,
                                 const float* resid_dev, const ttsc_conv1d_epilogue* ep, const int32_t* in_len_dev,
                                 const int32_t* out_len_dev, int64_t Lout_pitch, void* stream);
-/* Fused residual pair  y = x + conv2(lrelu(conv1(lrelu(x), 0.1), 0.1)) [+ y if accumulate]  of a HiFi-GAN ResBlock1
+/* Which kernel ttsc_conv1d_forward* launches for phase `phase` of the layer (0 unless the layer is a ConvTranspose1d that runs phase by phase) on a
+ * batch of B utterances of Lin positions with epilogue `ep` (NULL = none), under the environment's TTSC_CONV_* switches; the launcher calls the
+ * same selection.  No device is touched and no weights are needed: a handle from ttsc_conv1d_create + ttsc_conv1d_set_precision will do.
+ * Returns a path id, < 0 (and ttsc_last_error) for what the launch would refuse, and fills info[10] = {tile rows, tile columns, tap bucket
+ * (TTSC_CONV_PATH_F16X3: the TMAX of the instantiation, else 0), grid x, y, z, dynamic LDS bytes, lean, acc_init, short_from}:
+ *   TTSC_CONV_PATH_NONE    nothing: the phase has no output position inside the output
+ *   TTSC_CONV_PATH_COUT1   conv_cout1_kernel              one output channel (conv_post)
+ *   TTSC_CONV_PATH_TALL    conv_f16x3_tall_kernel         the first two upsamplers of HiFi-GAN V1
+ *   TTSC_CONV_PATH_WIDE    conv_f16x3_wide_kernel         square 128- / 256-channel ResBlock layers
+ *   TTSC_CONV_PATH_F16X3   conv_f16x3_kernel              the general split-precision kernel
+ *   TTSC_CONV_PATH_FP32    conv_mfma_kernel               the exact fp32 kernel */
+#define TTSC_CONV_PATH_NONE 0
+#define TTSC_CONV_PATH_COUT1 1
+#define TTSC_CONV_PATH_TALL 2
+#define TTSC_CONV_PATH_WIDE 3
+#define TTSC_CONV_PATH_F16X3 4
+#define TTSC_CONV_PATH_FP32 5
+int32_t ttsc_conv1d_plan(const ttsc_conv1d* c, int32_t B, int64_t Lin, const ttsc_conv1d_epilogue* ep, int32_t phase, int32_t* info);
+/* Fused residual pair y = x + conv2(lrelu(conv1(lrelu(x), 0.1), 0.1)) [+ y if accumulate]  of a HiFi-GAN ResBlock1
  * (both layers 32 -> 32 channels, odd kernel 3/7/11, conv2 undilated, both in TTSC_PREC_F16X3): the inner activation
  * stays in LDS, which removes two of the five HBM passes of the unfused pair.  `supported` returns 1 when the fused
  * kernel applies to the two layers; y must not alias x. */

@@ -329,6 +329,113 @@ def tiles_of(prec, mt):
     return {128: [(128, 128), (64, 128), (64, 64)], 64: [(64, 256), (64, 128), (64, 64)], 32: [(32, 512), (32, 256), (32, 128)]}[mt]
 
 
+# ---- the dispatch, restated (csrc/conv_plan.hpp; tests/test_conv_plan_cpu.py compares this with ttsc_conv1d_plan) --------------------------------
+
+PATH_NONE, PATH_COUT1, PATH_TALL, PATH_WIDE, PATH_F16X3, PATH_FP32 = range(6)   # TTSC_CONV_PATH_*
+INT_MAX = 2 ** 31 - 1
+FP32_NARROWER = {512: 256, 256: 128, 128: 64}   # the column count the fp32 fill rule weighs a tile's padding against
+
+
+class PlanError(ValueError):
+    pass
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def pipe_lds(span, mi):
+    """dynamic LDS of the wide / tall tile pipeline: two activation buffers of 4 planes + a dump slot pair, two weight slots, 16-byte items"""
+    return 2 * (4 * span + 2) * 16 + 2 * (2 * mi * 2 * 64) * 16
+
+
+def plan(cin, cout, k, B, Lin, prec='f16x3', stride=1, padding=0, dilation=1, transposed=False, groups=1, phase=0, gate=False, act=None,
+         out_scale=1.0, in_scale=1.0, wide=1, lean=True, tile=None):
+    """what ttsc_conv1d_forward launches for one phase of a layer: dict(family, rows, cols, tap_bucket, grid, lds, lean, acc_init, short_from).
+    wide / lean / tile are TTSC_CONV_WIDE / TTSC_CONV_LEAN / TTSC_CONV_TILE (tile: the variable's text or None); the once-per-process
+    switches are at their defaults.  Raises PlanError where the launch is refused."""
+    vfused = transposed and cout % 32 == 0 and stride > 1
+    if groups > 1:
+        cout_g, cin_g = cout // groups, cin // groups
+        mt = 128 if cout_g % 128 == 0 else (64 if cout_g % 64 == 0 else 32)
+        cin_tile = (mt // cout_g if mt > cout_g else 1) * cin_g
+    else:
+        mt, cin_tile = mt_class(cout, stride, transposed), cin
+    rows_v = stride * cout if vfused else cout
+    coutp, cinp = _cdiv(rows_v, mt) * mt, _cdiv(cin_tile, 16) * 16
+    # ttsc_conv1d_set_precision: the split kernel's register window holds 64 positions of halo and 16 taps; grouped layers are fp32 only
+    J = _cdiv(k, stride)
+    if prec == 'f16x3' and ((J - 1 if transposed else (k - 1) * dilation) > 64 or (J if transposed else k) > 16 or groups > 1):
+        prec = 'fp32'
+    f16 = prec == 'f16x3'
+    vrow4 = vfused and f16 and stride == 4 and k == 4 and padding == 0
+    Lout = out_len(Lin, k, stride, padding, dilation, transposed)
+    # the phase: taps and positions q with o = q * stride + r - padding inside [0, Lout)
+    if not transposed:
+        ntaps, halo, q_cnt = k, (k - 1) * dilation, Lout
+    else:
+        r_lo, r_hi = (stride - 1, 0) if vfused else (phase, phase)
+        ntaps = J if vfused else len(range(phase, k, stride))
+        qlo, qhi = -((r_lo - padding) // stride), (Lout - 1 - r_hi + padding) // stride + 1
+        if qhi <= qlo:
+            return dict(family=PATH_NONE, rows=0, cols=0, tap_bucket=0, grid=(0, 0, 0), lds=0, lean=0, acc_init=0, short_from=INT_MAX)
+        halo, q_cnt = ntaps - 1, qhi - qlo
+    forced = None
+    if tile:
+        parts = tile.lower().split('x')
+        if len(parts) != 2 or not all(s.isdigit() and int(s) > 0 for s in parts):
+            raise PlanError('malformed TTSC_CONV_TILE')
+        forced = (int(parts[0]), int(parts[1]))
+    p = dict(tap_bucket=0, lean=0, acc_init=0, short_from=INT_MAX)
+    if not transposed and groups == 1 and cout == 1 and cin <= 64 and k <= 16 and dilation == 1 and not gate:
+        return dict(p, family=PATH_COUT1, rows=1, cols=1024, grid=(_cdiv(Lout, 1024), B, 1), lds=0)
+    tiles = tiles_of(prec, mt)
+    if f16:
+        if ntaps > 16:
+            raise PlanError('more than 16 taps')
+        affine = act is None and f32(out_scale) == 1.0
+        small = B * cout * Lout < 2 ** 32
+        wide_shape = (not transposed and not gate and cin == cout and cout in (128, 256) and k in (3, 7, 11) and dilation in (1, 3, 5)
+                      and padding == dilation * (k - 1) // 2)
+        p['acc_init'] = int(bool(wide and wide_shape and affine and coutp == cout and small))
+        tall0 = cin == 512 and ntaps == 4 and coutp % 256 == 0
+        tall1 = cin == 256 and ntaps == 6 and coutp % 128 == 0
+        tall_shape = vfused and not vrow4 and not gate and cinp == cin and (tall0 or tall1)
+        trows, tcols = (256, 128) if tall0 else (128, 256)
+        s = f32(in_scale)
+        p['lean'] = int(bool(lean and cin * Lin * 4 < 2 ** 31 and s > 0 and np.isfinite(s)))
+        if tall_shape and trows == cout:
+            p['short_from'] = k - (ntaps - 1) * stride
+        if tall_shape and (wide == 2 or _cdiv(q_cnt, tcols) * (coutp // trows) * B >= 512):
+            nx, ny = _cdiv(q_cnt, tcols), coutp // trows
+            grid = (_cdiv(nx * B, 8) * 8 * ny, 1, 1) if ny > 1 else (nx, ny, B)   # (XCD-aware 1-D launch)
+            return dict(p, family=PATH_TALL, rows=trows, cols=tcols, grid=grid, lds=pipe_lds(tcols + ntaps - 1, trows // 64))
+        if wide and wide_shape and (wide == 2 or _cdiv(Lout, 256) * (cout // 128) * B >= 512):
+            return dict(p, family=PATH_WIDE, rows=128, cols=256, grid=(_cdiv(Lout, 256), cout // 128, B), lds=pipe_lds(256 + halo, 2))
+        p['tap_bucket'] = next(t for t in (3, 7, 11, 16) if ntaps <= t)
+
+    def wgs(t):
+        return _cdiv(q_cnt, t[1]) * (coutp // t[0]) * B
+
+    def fills(t):
+        if f16:
+            return wgs(t) >= 512
+        padded = lambda n: _cdiv(q_cnt, n) * n
+        return wgs(t) >= 512 and not padded(FP32_NARROWER[t[1]]) * 8 < padded(t[1]) * 7
+
+    if forced:
+        if forced not in tiles:
+            raise PlanError('not a tile of this layer')
+        t = forced
+    else:
+        t = next((u for u in tiles[:2] if fills(u)), tiles[2])
+    span = t[1] + halo
+    lds = span * 4 * 16 + ntaps * (t[0] // 32) * 2 * 64 * 16 if f16 else 2 * 16 * (span + 1) * 4
+    if not f16 and lds > 160 * 1024:
+        raise PlanError('receptive field too large for LDS')
+    return dict(p, family=PATH_F16X3 if f16 else PATH_FP32, rows=t[0], cols=t[1], grid=(_cdiv(q_cnt, t[1]), coutp // t[0], B), lds=lds)
+
+
 def tile_lengths(nt):
     """the lengths at which a tile of nt columns can go wrong: one column either side of a seam, more than one block, and one position (shorter
     than every receptive field here)"""

@@ -47,6 +47,24 @@ def _run(conv, c):
     return y.cpu()
 
 
+def _planned(conv, c):
+    """{(kernel family, tile rows, tile columns)} over the phases of the launch _run(conv, c) makes, from ttsc_conv1d_plan — the selection the
+    launcher itself calls, under the environment as it is now"""
+    from ttscube_amd import _lib
+    from ttscube_amd.hip_layers import ACT
+    kw = c['kw']
+    ep = _lib.Conv1dEpilogue(kw.get('in_scale', 1.0), kw.get('in_slope', 1.0), c.get('out_scale', 1.0), ACT[c.get('act')], int(c['acc0'] is not None), None, 1.0)
+    B, _, L = c['x'].shape
+    g = conv.cfg
+    info = (C.c_int32 * 10)()
+    out = set()
+    for ph in range(g.stride if g.transposed and g.out_channels % 32 else 1):
+        fam = _lib.lib().ttsc_conv1d_plan(conv._h, B, L, C.byref(ep), ph, info)
+        assert fam >= 0, _lib.lib().ttsc_last_error()
+        out.add((fam, info[0], info[1]))
+    return out - {(R.PATH_NONE, 0, 0)}
+
+
 def _ref64(c):
     return R.conv_f64(c['x'], c['w'], c['b'], resid=c['resid'], acc0=c['acc0'], out_scale=c.get('out_scale', 1.0), act=c.get('act'), **c['kw'])
 
@@ -87,6 +105,8 @@ def _layer_kw(layer, transposed):
 
 # ---- the general split kernel and the fp32 kernel, every tile ---------------------------------------------------------------------------------
 
+_GENERAL = {'f16x3': R.PATH_F16X3, 'fp32': R.PATH_FP32}
+
 def _general_params():
     out = []
     for prec in ('f16x3', 'fp32'):
@@ -101,13 +121,16 @@ def test_general_kernel_tile(prec, layer, transposed, tile, lengths, monkeypatch
     cin, cout, k, ds = layer
     variant = '%s-%dx%d%s' % (prec, tile[0], tile[1], '-transposed' if transposed else '')
     conv = None
+    planned = {(_GENERAL[prec],) + tile}
     for L in lengths:
         c = R.general_exact(layer, transposed, L)
         conv = conv or _layer_of(c, prec)
+        assert _planned(conv, c) == planned, (variant, layer, L)
         _check_exact(conv, c, (variant, layer, L))
     kw = dict(in_slope=0.1, **_layer_kw(layer, transposed))
     conv = _layer_of(R.cached_random(cin, cout, k, lengths[0], **kw)[0], prec)   # (the weights of a layer do not depend on L)
     for L in lengths:
+        assert _planned(conv, R.cached_random(cin, cout, k, L, **kw)[0]) == planned, (variant, layer, L)
         _check_random(variant, conv, cin, cout, k, L, **kw)
 
 
@@ -158,9 +181,13 @@ def test_general_kernel_ragged_and_tails(prec, monkeypatch):
             monkeypatch.setenv('TTSC_CONV_TILE', '%dx%d' % tile)
             nt = tile[1]
             c = dict(R.general_exact(layer, False, nt + 1), resid=None, acc0=None, exact=True)
-            _check_ragged_conv(_layer_of(c, prec), c, [nt + 1, 7], nt, (prec, layer, tile, 'exact'))
+            conv = _layer_of(c, prec)
+            assert _planned(conv, c) == {(_GENERAL[prec],) + tile}, (prec, layer, tile)
+            _check_ragged_conv(conv, c, [nt + 1, 7], nt, (prec, layer, tile, 'exact'))
             c = R.cached_random(layer[0], layer[1], layer[2], nt + 1, in_slope=0.1, dilation=layer[3])[0]
-            _check_ragged_conv(_layer_of(c, prec), c, [nt + 1, 7], nt, (prec, layer, tile, 'random'))
+            conv = _layer_of(c, prec)
+            assert _planned(conv, c) == {(_GENERAL[prec],) + tile}, (prec, layer, tile)
+            _check_ragged_conv(conv, c, [nt + 1, 7], nt, (prec, layer, tile, 'random'))
 
 
 def test_forced_tile_the_layer_cannot_take_is_an_error(monkeypatch):
@@ -205,8 +232,11 @@ def test_wide_kernel(C_, k, d, L, monkeypatch):
     variant = 'wide-%d' % C_
     c = R.exact_case(C_, C_, k, L, dilation=d, in_slope=0.5)
     conv = _layer_of(c, 'f16x3')
+    assert _planned(conv, c) == {(R.PATH_WIDE, 128, 256)}
     _check_exact(conv, c, (variant, k, d, L, 'plain'))
-    _check_exact(conv, R.exact_case(C_, C_, k, L, dilation=d, resid=True, acc0=True, in_scale=0.5, in_slope=0.25), (variant, k, d, L, 'acc_init'))
+    c = R.exact_case(C_, C_, k, L, dilation=d, resid=True, acc0=True, in_scale=0.5, in_slope=0.25)
+    assert _planned(conv, c) == {(R.PATH_WIDE, 128, 256)}
+    _check_exact(conv, c, (variant, k, d, L, 'acc_init'))
     if L in (5, 257):   # (one full length per (C, K, d) pays for the yardstick: about a second at 256 channels with K = 11)
         conv = _layer_of(R.cached_random(C_, C_, k, L, dilation=d, in_slope=0.1)[0], 'f16x3')
         _check_random(variant, conv, C_, C_, k, L, dilation=d, in_slope=0.1)
@@ -239,10 +269,13 @@ def test_batch_size_never_changes_a_bit_on_the_wide_layers(C_, k, monkeypatch):
         conv = _layer_of(c, 'f16x3')
         monkeypatch.setenv('TTSC_CONV_WIDE', '2')
         monkeypatch.delenv('TTSC_CONV_TILE', raising=False)
+        assert _planned(conv, c) == {(R.PATH_WIDE, 128, 256)}
         wide = _run(conv, c)
         monkeypatch.setenv('TTSC_CONV_WIDE', '1')   # the default: a problem this small goes to the general kernel
+        assert _planned(conv, c) == {(R.PATH_F16X3, 32, 128)}   # (and to its smallest tile: 8 and 16 workgroups of the larger ones)
         for tile in R.tiles_of('f16x3', R.mt_class(C_)):
             monkeypatch.setenv('TTSC_CONV_TILE', '%dx%d' % tile)
+            assert _planned(conv, c) == {(R.PATH_F16X3,) + tile}
             y = _run(conv, c)
             assert torch.equal(y, wide), (C_, k, tile, sorted(extra), float((y - wide).abs().max()))
 
@@ -272,6 +305,7 @@ def test_tall_kernel(cin, cout, k, s, L, monkeypatch):
     monkeypatch.setenv('TTSC_CONV_TILE', '32x512')   # not a tile of this layer: the tall kernel does not read the switch
     c = R.exact_case(cin, cout, k, L, stride=s, transposed=True, in_slope=0.25)
     conv = _layer_of(c, 'f16x3')
+    assert _planned(conv, c) == {(R.PATH_TALL,) + ((256, 128) if cin == 512 else (128, 256))}
     _check_exact(conv, c, ('tall', cin, L))           # the whole output: every phase
     conv = _layer_of(R.cached_random(cin, cout, k, L, stride=s, transposed=True, in_slope=0.1)[0], 'f16x3')
     _check_random('tall-%d' % cin, conv, cin, cout, k, L, stride=s, transposed=True, in_slope=0.1)
@@ -282,6 +316,7 @@ def test_tall_kernel(cin, cout, k, s, L, monkeypatch):
 def test_cout1_kernel(cin, L, prec):
     c = R.exact_case(cin, 1, 7, L, resid=True, acc0=True, in_scale=0.5, in_slope=0.25)
     conv = _layer_of(c, prec)
+    assert _planned(conv, c) == {(R.PATH_COUT1, 1, 1024)}
     _check_exact(conv, c, ('cout1', cin, L))
     kw = dict(resid=True, acc0=True, in_slope=0.01)
     conv = _layer_of(R.cached_random(cin, 1, 7, L, **kw)[0], prec)

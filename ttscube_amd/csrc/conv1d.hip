@@ -355,18 +355,38 @@ static int launch_cfg(const ConvArgs& a, int B, hipStream_t s) {
     return launch_checked("conv_mfma_kernel");
 }
 
-// TTSC_CONV_TILE=<rows>x<cols> forces the tile of the general split kernel and of the fp32 kernel (tests: every tile variant at small shapes).
-// Read at every launch, like TTSC_CONV_WIDE.  0 = unset, 1 = parsed, -1 = malformed.  A tile the layer cannot take is an error at the launch,
-// never another tile: the error is what proves which variant ran.
-static int forced_tile(int* rows, int* cols) {
-    const char* ev = getenv("TTSC_CONV_TILE");
-    if (!ev || !*ev) return 0;
-    int r = 0, c = 0;
-    char x = 0, tail = 0;
-    if (sscanf(ev, "%d%c%d%c", &r, &x, &c, &tail) != 3 || (x != 'x' && x != 'X') || r <= 0 || c <= 0) return -1;
-    *rows = r;
-    *cols = c;
-    return 1;
+static long env_num(const char* name, long unset) {
+    const char* ev = getenv(name);
+    return ev ? atol(ev) : unset;
+}
+
+// The ONE place that reads the environment switches of the convolution dispatch (docs/KERNELS.md lists them); conv_plan decides from the values.
+static ConvSwitches conv_switches() {
+    // measurement switches, read once per process
+    static const ConvSwitches once = [] {
+        ConvSwitches s;
+        s.big_only = env_num("TTSC_F16_TILE", 1) == 0;
+        s.acc_init = (int)env_num("TTSC_CONV_ACC_INIT", 1);
+        s.tall = env_num("TTSC_CONV_TALL", 1) != 0;
+        s.want = env_num("TTSC_CONV_WANT", 512);
+        s.narrow = (int)env_num("TTSC_CONV_NARROW", 1);
+        s.epi_prefetch = (int)env_num("TTSC_CONV_EPI_PREFETCH", 1);
+        s.tall_swizzle = (int)env_num("TTSC_TALL_SWIZZLE", 1);
+        return s;
+    }();
+    // test switches, read at every launch so that one process can compare the variants
+    ConvSwitches s = once;
+    s.wide = (int)env_num("TTSC_CONV_WIDE", 1);
+    s.lean = env_num("TTSC_CONV_LEAN", 1) != 0;
+    // TTSC_CONV_TILE=<rows>x<cols> forces the tile of the general split kernel and of the fp32 kernel (tests: every tile variant at small shapes).
+    // A tile the layer cannot take is an error at the launch, never another tile: the error is what proves which variant ran.
+    if (const char* ev = getenv("TTSC_CONV_TILE"); ev && *ev) {
+        char x = 0, tail = 0;
+        const bool ok = sscanf(ev, "%d%c%d%c", &s.tile_rows, &x, &s.tile_cols, &tail) == 3 && (x == 'x' || x == 'X') && s.tile_rows > 0 && s.tile_cols > 0;
+        s.tile_state = ok ? 1 : -1;
+        s.tile_text = ev;
+    }
+    return s;
 }
 
 static int pick_mt(int Cout) {
@@ -541,6 +561,9 @@ extern "C" int ttsc_conv1d_set_precision(ttsc_conv1d* c, int32_t precision) {
     if (precision == c->precision) return TTSC_OK;
     TTSC_REQUIRE(!c->dev_weights, "ttsc_conv1d_set_precision: weights were set from device memory; switch the precision first");
     c->precision = precision;
+    // kernel_size == stride == 4 (the last two upsamplers of HiFi-GAN V1): the split path interleaves the virtual rows so that a lane's
+    // accumulator registers are four consecutive output samples (epilogue_tile_v4).  The precision changes nowhere else.
+    c->vrow4 = conv_vrow4(c->cfg, c->vfused, precision);
     return c->has_weight ? conv_repack(c) : TTSC_OK;
 }
 
@@ -682,74 +705,24 @@ static int conv_repack(ttsc_conv1d* c) {
         wscale = ldexpf(1.f, e);
         c->w_unscale = ldexpf(1.f, -e);
     }
-    // kernel_size == stride == 4 (the last two upsamplers of HiFi-GAN V1): interleave the virtual rows so that a lane's
-    // accumulator registers are four consecutive output samples (epilogue_tile_v4)
-    c->vrow4 = c->vfused && c->precision == TTSC_PREC_F16X3 && g.stride == 4 && g.kernel_size == 4 && g.padding == 0;
-    std::vector<int> cur_taps;
-    auto upload = [&](ConvPhase& ph) -> int {
+    // the phases are a function of the configuration (conv_plan.hpp); here they get their packed weights
+    const std::vector<ConvPhaseGeom> geom = conv_phases(g, c->vfused);
+    if (g.transposed) {   // (phase by phase: some phase would have no tap)
+        TTSC_REQUIRE(g.kernel_size >= g.stride, "ConvTranspose1d with kernel_size < stride is not supported");
+    }
+    for (const ConvPhaseGeom& pg : geom) {
+        ConvPhase ph;
+        static_cast<ConvPhaseGeom&>(ph) = pg;
         if (c->precision == TTSC_PREC_F16X3) {
-            pack_phase_f16(c, w, cur_taps, wscale, packed_h);
+            pack_phase_f16(c, w, ph.taps, wscale, packed_h);
             TTSC_HIP_CHECK(hipMalloc((void**)&ph.wph_dev, packed_h.size() * sizeof(_Float16)));
             TTSC_HIP_CHECK(hipMemcpy(ph.wph_dev, packed_h.data(), packed_h.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-            return TTSC_OK;
+        } else {
+            pack_phase(c, w, ph.taps, packed);
+            TTSC_HIP_CHECK(hipMalloc((void**)&ph.wp_dev, packed.size() * sizeof(float)));
+            TTSC_HIP_CHECK(hipMemcpy(ph.wp_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
         }
-        pack_phase(c, w, cur_taps, packed);
-        TTSC_HIP_CHECK(hipMalloc((void**)&ph.wp_dev, packed.size() * sizeof(float)));
-        TTSC_HIP_CHECK(hipMemcpy(ph.wp_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        return TTSC_OK;
-    };
-    if (!g.transposed) {
-        ConvPhase ph;
-        std::vector<int> taps;
-        for (int k = 0; k < g.kernel_size; ++k) taps.push_back(k);
-        ph.ntaps = g.kernel_size;
-        ph.tap_base = -g.padding;
-        ph.tap_step = g.dilation;
-        ph.out_stride = 1;
-        ph.out_off = 0;
-        cur_taps = taps;
-        ph.taps = taps;
-        int rc = upload(ph);
-        if (rc) return rc;
         c->phases.push_back(ph);
-    } else if (c->vfused) {
-        ConvPhase ph;
-        std::vector<int> taps;
-        const int J = (g.kernel_size + g.stride - 1) / g.stride;
-        for (int j = 0; j < J; ++j) taps.push_back(j);   // tap INDEX; the packers map (phase, index) -> kernel tap
-        ph.r = -1;
-        ph.ntaps = J;
-        ph.tap_base = 0;
-        ph.tap_step = -1;
-        ph.out_stride = g.stride;
-        ph.out_off = -g.padding;
-        cur_taps = taps;
-        ph.taps = taps;
-        int rc = upload(ph);
-        if (rc) return rc;
-        c->phases.push_back(ph);
-    } else {
-        for (int r = 0; r < g.stride; ++r) {
-            ConvPhase ph;
-            std::vector<int> taps;
-            for (int k = r; k < g.kernel_size; k += g.stride) taps.push_back(k);
-            if (taps.empty()) continue;  // K < stride: this phase only gets the bias (handled below)
-            ph.r = r;
-            ph.ntaps = (int)taps.size();
-            ph.tap_base = 0;
-            ph.tap_step = -1;
-            ph.out_stride = g.stride;
-            ph.out_off = r - g.padding;
-            cur_taps = taps;
-            ph.taps = taps;
-            int rc = upload(ph);
-            if (rc) return rc;
-            c->phases.push_back(ph);
-        }
-        TTSC_REQUIRE((int)c->phases.size() == g.stride, "ConvTranspose1d with kernel_size < stride is not supported");
-    }
-    if (g.transposed) {
-        TTSC_REQUIRE(g.kernel_size >= g.stride, "ConvTranspose1d with kernel_size < stride is not supported");
     }
     if (c->bias_dev) {
         (void)hipFree(c->bias_dev);
@@ -763,7 +736,7 @@ static int conv_repack(ttsc_conv1d* c) {
         (void)hipFree(c->w_plain_dev);
         c->w_plain_dev = nullptr;
     }
-    if (!g.transposed && g.out_channels == 1) {   // conv_cout1_kernel reads the weights in torch layout [1][Cin][K]
+    if (conv_wants_plain(g)) {   // conv_cout1_kernel reads the weights in torch layout [1][Cin][K]
         TTSC_HIP_CHECK(hipMalloc((void**)&c->w_plain_dev, c->w_host.size() * sizeof(float)));
         TTSC_HIP_CHECK(hipMemcpy(c->w_plain_dev, c->w_host.data(), c->w_host.size() * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -833,6 +806,19 @@ extern "C" int ttsc_absmax(const float* x_dev, int64_t n, float* out_dev, void* 
     return launch_checked("absmax_kernel");
 }
 
+// the plan's LDS size of the wide and tall kernels is the pipeline's
+static_assert(WidePipe<256, 11, 5, true>::LDS_BYTES == conv_pipe_lds(256 + 10 * 5, 2) && TallPipe<512, 4, 4, 2, true>::LDS_BYTES == conv_pipe_lds(128 + 3, 4) &&
+              TallPipe<256, 6, 2, 4, false>::LDS_BYTES == conv_pipe_lds(256 + 5, 2), "conv_plan.hpp: conv_pipe_lds");
+
+// conv_plan's view of a handle and of a call.  Without weights the plain-layout copy counts as present when set_weight would create it.
+static ConvLayer conv_layer_of(const ttsc_conv1d* c) {
+    const bool has_plain = c->has_weight ? (c->dev_weights ? c->w_plain_ext : c->w_plain_dev) != nullptr : conv_wants_plain(c->cfg);
+    return ConvLayer{c->cfg, c->MT, c->NT, c->CinP, c->CoutP, c->groups, c->precision, c->vfused, c->vrow4, has_plain, c->act_scale};
+}
+static ConvLaunch conv_launch_of(int B, int64_t Lin, int64_t Lout, const ttsc_conv1d_epilogue* ep) {
+    return ConvLaunch{B, Lin, Lout, ep && ep->gate_dev, ep ? ep->out_act : TTSC_ACT_NONE, ep ? ep->out_scale : 1.f, ep ? ep->in_scale : 1.f};
+}
+
 extern "C" int ttsc_conv1d_forward_ragged(const ttsc_conv1d* c, const float* x, int32_t B, int64_t Lin, float* y,
                                           const float* resid, const ttsc_conv1d_epilogue* ep, const int32_t* in_len_dev,
                                           const int32_t* out_len_dev, void* stream) {
@@ -857,7 +843,11 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
     TTSC_REQUIRE(Lout > 0, "ttsc_conv1d_forward: output length %lld <= 0", (long long)Lout);
     TTSC_REQUIRE(Lin < (1ll << 30) && Lout < (1ll << 30), "ttsc_conv1d_forward: length too large");
     hipStream_t s = (hipStream_t)stream;
+    const ConvSwitches sw = conv_switches();
+    const ConvLayer layer = conv_layer_of(c);
+    const ConvLaunch launch = conv_launch_of(B, Lin, Lout, ep);
     for (const auto& ph : c->phases) {
+        // 1. what does not depend on the plan
         ConvArgs a;
         a.x = x;
         a.y = y;
@@ -870,12 +860,7 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
         a.in_len = in_len_dev;
         a.out_len = out_len_dev;
         a.dbg = 0;
-        a.acc_init = 0;
-        a.epi_prefetch = 0;
-        a.swz_nx = a.swz_ny = 0;
-        a.lean = 0;
-        a.short_from = INT_MAX;
-        a.fold_S = a.fold_B = 0;
+        a.fold_S = 0;
         a.amax_x = a.amax_w = nullptr;
         a.amax_out = nullptr;
 #ifdef TTSC_ABLATE
@@ -883,7 +868,7 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
         a.prof = nullptr;
         if (const char* ev = getenv("TTSC_PROF_PTR")) a.prof = reinterpret_cast<unsigned long long*>(strtoull(ev, nullptr, 0));
 #endif
-        a.vphase = c->vfused ? ((c->vrow4 && c->precision == TTSC_PREC_F16X3) ? -4 : g.out_channels) : 0;
+        a.vphase = c->vfused ? (c->vrow4 ? -4 : g.out_channels) : 0;
         if (a.vphase == -4) {
             TTSC_REQUIRE(!(ep && ep->gate_dev), "ttsc_conv1d_forward: the gate epilogue is not available on this transposed layer");
             TTSC_REQUIRE(((uintptr_t)y % 16 == 0) && (!resid || (uintptr_t)resid % 16 == 0), "ttsc_conv1d_forward: y / resid must be 16-byte aligned for ConvTranspose1d(k=4, s=4)");
@@ -903,199 +888,97 @@ extern "C" int ttsc_conv1d_forward_pitched(const ttsc_conv1d* c, const float* x,
         a.tap_step = ph.tap_step;
         a.out_stride = ph.out_stride;
         a.out_off = ph.out_off;
-        if (!g.transposed) {
-            a.q_lo = 0;
-            a.q_cnt = (int)Lout;
-        } else if (c->vfused) {
-            // union over the phases r = 0..s-1 of  o = q*s + r - p in [0, Lout); per-element validity is checked in the epilogue
-            int64_t qlo = -floor_div((g.stride - 1) - g.padding, g.stride);
-            int64_t qhi = floor_div(Lout - 1 + g.padding, g.stride) + 1;
-            if (qhi <= qlo) continue;
-            a.q_lo = (int)qlo;
-            a.q_cnt = (int)(qhi - qlo);
-        } else {
-            // o = q*s + r - p in [0, Lout)
-            int64_t qlo = -floor_div(ph.r - g.padding, g.stride);  // ceil((p - r) / s)
-            int64_t qhi = floor_div(Lout - 1 - ph.r + g.padding, g.stride) + 1;      // exclusive
-            if (qhi <= qlo) continue;
-            a.q_lo = (int)qlo;
-            a.q_cnt = (int)(qhi - qlo);
-        }
-        const int last = (ph.ntaps - 1) * ph.tap_step;
-        a.min_shift = ph.tap_base + (last < 0 ? last : 0);
-        a.span = c->NT + (last < 0 ? -last : last);
-        a.span_pad = a.span + 1;
-        a.in_scale = ep ? ep->in_scale : 1.f;
-        const float* w_plain = c->dev_weights ? c->w_plain_ext : c->w_plain_dev;
-        const bool use_cout1 = !g.transposed && c->groups == 1 && g.out_channels == 1 && g.in_channels <= 64 && g.kernel_size <= 16 && g.dilation == 1 &&
-                               w_plain && !(ep && ep->gate_dev);
-        if (c->precision == TTSC_PREC_F16X3 && !use_cout1) {   // activation pre-scale (exact powers of two, see ttsc_conv1d_set_activation_scale)
-            a.in_scale *= c->act_scale;
-            a.w_unscale = c->w_unscale / c->act_scale;
-        }
+        a.in_scale = launch.in_scale;
         a.in_slope = ep ? ep->in_slope : 1.f;
-        a.out_scale = ep ? ep->out_scale : 1.f;
-        a.out_act = ep ? ep->out_act : TTSC_ACT_NONE;
+        a.out_scale = launch.out_scale;
+        a.out_act = launch.out_act;
         a.accumulate = ep ? ep->accumulate : 0;
         a.gate = ep ? ep->gate_dev : nullptr;
         a.gate_slope = ep ? ep->gate_slope : 1.f;
-        int rc;
-        int ft_rows = 0, ft_cols = 0;
-        const int ft_rc = forced_tile(&ft_rows, &ft_cols);
-        TTSC_REQUIRE(ft_rc >= 0, "ttsc_conv1d_forward: TTSC_CONV_TILE must be <rows>x<cols>, e.g. 64x256 (got '%s')", getenv("TTSC_CONV_TILE"));
-        const bool ft_set = ft_rc > 0;
-        if (use_cout1) {
-            // one output channel (conv_post): vector-ALU kernel, bound by the single read of its input
-            a.wp = w_plain;
-            a.nf_flag = c->nf_flag;
-            dim3 grid((unsigned)ceil_div(Lout, 1024), (unsigned)B);
-            hipLaunchKernelGGL(conv_cout1_kernel, grid, dim3(256), 0, s, a);
-            rc = launch_checked("conv_cout1_kernel");
-        } else if (c->precision == TTSC_PREC_F16X3) {
-            // the split kernel's N tile is fixed by its 4-waves-along-N shape
-            const int nt = c->MT >= 64 ? 256 : 512;
-            a.span = nt + (last < 0 ? -last : last);
-            a.span_pad = a.span;
-            TTSC_REQUIRE(ph.ntaps <= 16, "f16x3 path supports at most 16 taps per phase (got %d)", ph.ntaps);
-            // tile by machine fill (same rule as the fp32 path): a single short utterance (the reference API's B=1 case)
-            // has only a few thousand positions per layer, so the big tiles would occupy a fraction of the 256 CUs
-            auto wgs16 = [&](int mt, int nt) { return (long)ceil_div(a.q_cnt, nt) * (c->CoutP / mt) * B; };
-            auto set_nt16 = [&](int n) {
-                a.span = n + (last < 0 ? -last : last);
-                a.span_pad = a.span;
-            };
-            static const bool big_only = getenv("TTSC_F16_TILE") && atoi(getenv("TTSC_F16_TILE")) == 0;
-            const char* wide_ev = getenv("TTSC_CONV_WIDE");
-            const int wide_env = wide_ev ? atoi(wide_ev) : 1;   // 0 = off, 2 = also for problems too small to fill the chip (tests)
-            const long want16 = 512;
-            // square "same"-padded layers of the wide stages (the generator's ResBlock convolutions at 128 / 256 channels):
-            // the wide-tile kernel (activation window staged once for all output channels)
-            const bool wide_shape = !g.transposed && !a.gate && g.in_channels == g.out_channels &&
-                                    (g.out_channels == 128 || g.out_channels == 256) &&
-                                    ((g.kernel_size == 3 || g.kernel_size == 7 || g.kernel_size == 11)
-#ifdef TTSC_PROBE_EVENK
-                                     || ((g.kernel_size == 4 || g.kernel_size == 6) && g.dilation == 1)
-#endif
-                                     ) &&
-                                    (g.dilation == 1 || g.dilation == 3 || g.dilation == 5) &&
-                                    g.padding == g.dilation * (g.kernel_size - 1) / 2;
-            // these layers start their sums at (residual + running sum + bias) / w_unscale in BOTH kernels that may run them (same bits whichever
-            // the fill rule picks); TTSC_CONV_ACC_INIT=0 puts the operands back into the epilogue (measurement switch)
-            static const int acc_init_env = getenv("TTSC_CONV_ACC_INIT") ? atoi(getenv("TTSC_CONV_ACC_INIT")) : 1;
-            a.acc_init = (acc_init_env && wide_env && wide_shape && a.out_act == TTSC_ACT_NONE && a.out_scale == 1.f && c->CoutP == g.out_channels &&
-                          (size_t)B * g.out_channels * Lout < (1ull << 32)) ? 1 : 0;
-            // the first upsamplers of the V1 generator: tall tiles (256 virtual rows x 128 input positions)
-            static const bool tall_on = !(getenv("TTSC_CONV_TALL") && atoi(getenv("TTSC_CONV_TALL")) == 0);
-            const bool tall0 = g.in_channels == 512 && ph.ntaps == 4 && c->CoutP % 256 == 0;    // ups.0: 256-row tiles
-            const bool tall1 = g.in_channels == 256 && ph.ntaps == 6 && c->CoutP % 128 == 0;    // ups.1: 128-row tiles
-            const bool tall_shape = tall_on && c->vfused && a.vphase > 0 && !a.gate && c->CinP == g.in_channels && (tall0 || tall1);
-            // lean staging and zero-tap skipping of the wide and tall kernels (see LEAN_OOB): TTSC_CONV_LEAN=0 launches the kernels as they were.  Read
-            // at every launch, like TTSC_CONV_WIDE, so that one process can compare the two.  The buffer path needs 32-bit byte offsets into one
-            // utterance's input with room for the out-of-range marker, and an in_scale for which 0 * in_scale is +0.
-            const char* lean_ev = getenv("TTSC_CONV_LEAN");
-            a.lean = (!(lean_ev && atoi(lean_ev) == 0) && (int64_t)g.in_channels * Lin * 4 < (1ll << 31) && a.in_scale > 0.f && std::isfinite(a.in_scale)) ? 1 : 0;
-            // tall kernel: a row tile that is exactly one phase r lacks the last tap when r + (J - 1) * stride >= kernel_size; a tile that spans
-            // phases keeps all J taps
-            if (tall_shape && (tall0 ? 256 : 128) == g.out_channels) a.short_from = g.kernel_size - (ph.ntaps - 1) * g.stride;
-            if (tall_shape && (wide_env == 2 || (long)ceil_div(a.q_cnt, tall0 ? 128 : 256) * (c->CoutP / (tall0 ? 256 : 128)) * B >= want16)) {
-                rc = tall0 ? launch_f16_tall<512, 4, 4, 2>(a, B, s) : launch_f16_tall<256, 6, 2, 4>(a, B, s);
-            } else if (wide_env && wide_shape && (wide_env == 2 || (long)ceil_div(a.Lout, 256) * (g.out_channels / 128) * B >= want16)) {
-                if (g.out_channels == 256)
-                    rc = launch_f16_wide_k<256>(a, B, g.dilation, s);
-                else
-                    rc = launch_f16_wide_k<128>(a, B, g.dilation, s);
-            } else if (ft_set) {
-                // forced tile: one of the three the fill rule below could pick for this MT class, through the same span bookkeeping
-                const bool m64 = c->MT >= 64;
-                if (m64 && ft_rows == 64 && ft_cols == 256) {
-                    rc = launch_f16<2, 2>(a, B, s);
-                } else if (m64 && ft_rows == 64 && ft_cols == 128) {
-                    set_nt16(128);
-                    rc = launch_f16<2, 1>(a, B, s);
-                } else if (!m64 && ft_rows == 32 && ft_cols == 512) {
-                    rc = launch_f16<1, 4>(a, B, s);
-                } else if (!m64 && ft_rows == 32 && ft_cols == 256) {
-                    set_nt16(256);
-                    rc = launch_f16<1, 2>(a, B, s);
-                } else if (ft_rows == 32 && ft_cols == 128) {
-                    set_nt16(128);
-                    rc = launch_f16<1, 1>(a, B, s);
-                } else {
-                    set_error("ttsc_conv1d_forward: TTSC_CONV_TILE=%dx%d is not a split-kernel tile of this layer (MT %d: %s, 32x128)", ft_rows, ft_cols,
-                              c->MT, m64 ? "64x256, 64x128" : "32x512, 32x256");
-                    return TTSC_EINVAL;
+        // 2. kernel family, tile and what follows from them
+        ConvPlan p;
+        if (!conv_plan(layer, ph, launch, sw, p)) {
+            set_error("%s", p.error);
+            return TTSC_EINVAL;
+        }
+        if (p.family == TTSC_CONV_PATH_NONE) continue;
+        // 3. the plan's part of the arguments
+        a.q_lo = p.q_lo;
+        a.q_cnt = p.q_cnt;
+        a.min_shift = p.min_shift;
+        a.span = p.span;
+        a.span_pad = p.span_pad;
+        a.acc_init = p.acc_init;
+        a.epi_prefetch = p.epi_prefetch;
+        a.swz_nx = p.swz_nx;
+        a.swz_ny = p.swz_ny;
+        a.fold_B = p.fold_B;
+        a.lean = p.lean;
+        a.short_from = p.short_from;
+        if (c->precision == TTSC_PREC_F16X3 && p.family != TTSC_CONV_PATH_COUT1) {   // activation pre-scale (exact powers of two, see ttsc_conv1d_set_activation_scale)
+            a.in_scale *= c->act_scale;
+            a.w_unscale = c->w_unscale / c->act_scale;
+        }
+        // 4. the instantiation the plan names
+        int rc = TTSC_EINVAL;
+        switch (p.family) {
+            case TTSC_CONV_PATH_COUT1:
+                a.wp = c->dev_weights ? c->w_plain_ext : c->w_plain_dev;
+                a.nf_flag = c->nf_flag;
+                hipLaunchKernelGGL(conv_cout1_kernel, dim3(p.grid[0], p.grid[1]), dim3(256), 0, s, a);
+                rc = launch_checked("conv_cout1_kernel");
+                break;
+            case TTSC_CONV_PATH_TALL:
+                rc = p.inst == 0 ? launch_f16_tall<512, 4, 4, 2>(a, B, s) : launch_f16_tall<256, 6, 2, 4>(a, B, s);
+                break;
+            case TTSC_CONV_PATH_WIDE:
+                rc = g.out_channels == 256 ? launch_f16_wide_k<256>(a, B, g.dilation, s) : launch_f16_wide_k<128>(a, B, g.dilation, s);
+                break;
+            case TTSC_CONV_PATH_F16X3:
+                switch (p.inst) {
+                    case F16_2x2: rc = launch_f16<2, 2>(a, B, s); break;
+                    case F16_2x1: rc = launch_f16<2, 1>(a, B, s); break;
+                    case F16_1x4: rc = launch_f16<1, 4>(a, B, s); break;
+                    case F16_1x2: rc = launch_f16<1, 2>(a, B, s); break;
+                    case F16_1x1: rc = launch_f16<1, 1>(a, B, s); break;
                 }
-            } else if (c->MT >= 64) {
-                if (big_only || wgs16(64, 256) >= want16)
-                    rc = launch_f16<2, 2>(a, B, s);   // 64 x 256 tile (MT=128 layers run as two M tiles)
-                else if (wgs16(64, 128) >= want16) {
-                    set_nt16(128);
-                    rc = launch_f16<2, 1>(a, B, s);
-                } else {
-                    set_nt16(128);
-                    rc = launch_f16<1, 1>(a, B, s);
+                break;
+            case TTSC_CONV_PATH_FP32:
+                switch (p.inst) {
+                    case CFG_2222: rc = launch_cfg<2, 2, 2, 2>(a, B, s); break;
+                    case CFG_1222: rc = launch_cfg<1, 2, 2, 2>(a, B, s); break;
+                    case CFG_1122: rc = launch_cfg<1, 1, 2, 2>(a, B, s); break;
+                    case CFG_2214: rc = launch_cfg<2, 2, 1, 4>(a, B, s); break;
+                    case CFG_1414: rc = launch_cfg<1, 4, 1, 4>(a, B, s); break;
+                    case CFG_1214: rc = launch_cfg<1, 2, 1, 4>(a, B, s); break;
+                    case CFG_1114: rc = launch_cfg<1, 1, 1, 4>(a, B, s); break;
                 }
-            } else {
-                if (big_only || wgs16(32, 512) >= want16)
-                    rc = launch_f16<1, 4>(a, B, s);   // 32 x 512 tile
-                else if (wgs16(32, 256) >= want16) {
-                    set_nt16(256);
-                    rc = launch_f16<1, 2>(a, B, s);
-                } else {
-                    set_nt16(128);
-                    rc = launch_f16<1, 1>(a, B, s);
-                }
-            }
-        } else {
-            // fp32 tile by machine fill: the largest tile that still gives >= 2 workgroups per CU (training crops and
-            // single short utterances are small problems: a 128 x 128 tile would leave most of the 256 CUs idle)
-            auto wgs = [&](int mt, int nt) { return (long)ceil_div(a.q_cnt, nt) * (c->CoutP / mt) * B; };
-            auto set_nt = [&](int nt) {
-                a.span = nt + (last < 0 ? -last : last);
-                a.span_pad = a.span + 1;
-            };
-            static const long want_env = getenv("TTSC_CONV_WANT") ? atol(getenv("TTSC_CONV_WANT")) : 512;
-            static const int narrow_env = getenv("TTSC_CONV_NARROW") ? atoi(getenv("TTSC_CONV_NARROW")) : 1;
-            const long want = want_env;
-            // ... and, among the tiles that fill the machine, not one that is mostly padding: the deep layers of the discriminators see
-            // sequences of 50-200 positions (a 128-column tile over 149 positions computes 256), so a narrower tile is taken whenever it
-            // cuts the padded columns by more than an eighth (this kernel is bound by its MFMA count, not by operand reuse)
-            auto padded = [&](int nt) { return (long)ceil_div(a.q_cnt, nt) * nt; };
-            auto narrower_pays = [&](int nt_big, int nt_small) { return narrow_env && padded(nt_small) * 8 < padded(nt_big) * 7; };
-            if (ft_set) {
-                // forced tile: one of the three the fill rule below could pick for this MT class
-                const int mt = c->MT, r = ft_rows, n = ft_cols;
-                if (mt == 128 && r == 128 && n == 128) { set_nt(128); rc = launch_cfg<2, 2, 2, 2>(a, B, s); }
-                else if (mt >= 64 && r == 64 && n == 128) { set_nt(128); rc = launch_cfg<1, 2, 2, 2>(a, B, s); }
-                else if (mt >= 64 && r == 64 && n == 64) { set_nt(64); rc = launch_cfg<1, 1, 2, 2>(a, B, s); }
-                else if (mt == 64 && r == 64 && n == 256) { set_nt(256); rc = launch_cfg<2, 2, 1, 4>(a, B, s); }
-                else if (mt == 32 && r == 32 && n == 512) { set_nt(512); rc = launch_cfg<1, 4, 1, 4>(a, B, s); }
-                else if (mt == 32 && r == 32 && n == 256) { set_nt(256); rc = launch_cfg<1, 2, 1, 4>(a, B, s); }
-                else if (mt == 32 && r == 32 && n == 128) { set_nt(128); rc = launch_cfg<1, 1, 1, 4>(a, B, s); }
-                else {
-                    set_error("ttsc_conv1d_forward: TTSC_CONV_TILE=%dx%d is not an fp32 tile of this layer (MT %d: %s)", r, n, mt,
-                              mt == 128 ? "128x128, 64x128, 64x64" : (mt == 64 ? "64x256, 64x128, 64x64" : "32x512, 32x256, 32x128"));
-                    return TTSC_EINVAL;
-                }
-            } else if (c->MT == 128) {
-                if (wgs(128, 128) >= want && !narrower_pays(128, 64)) { set_nt(128); rc = launch_cfg<2, 2, 2, 2>(a, B, s); }
-                else if (wgs(64, 128) >= want && !narrower_pays(128, 64)) { set_nt(128); rc = launch_cfg<1, 2, 2, 2>(a, B, s); }
-                else { set_nt(64); rc = launch_cfg<1, 1, 2, 2>(a, B, s); }
-            } else if (c->MT == 64) {
-                if (wgs(64, 256) >= want && !narrower_pays(256, 128)) { set_nt(256); rc = launch_cfg<2, 2, 1, 4>(a, B, s); }
-                else if (wgs(64, 128) >= want && !narrower_pays(128, 64)) { set_nt(128); rc = launch_cfg<1, 2, 2, 2>(a, B, s); }
-                else { set_nt(64); rc = launch_cfg<1, 1, 2, 2>(a, B, s); }
-            } else {
-                if (wgs(32, 512) >= want && !narrower_pays(512, 256)) { set_nt(512); rc = launch_cfg<1, 4, 1, 4>(a, B, s); }
-                else if (wgs(32, 256) >= want && !narrower_pays(256, 128)) { set_nt(256); rc = launch_cfg<1, 2, 1, 4>(a, B, s); }
-                else { set_nt(128); rc = launch_cfg<1, 1, 1, 4>(a, B, s); }
-            }
+                break;
         }
         if (rc) return rc;
     }
     return TTSC_OK;
 }
 
+// Which kernel the launcher above takes, without launching: the same conv_switches(), the same conv_plan() — the query cannot drift from the
+// launcher.  No HIP call; a handle without weights plans the phases (and the plain-layout copy) ttsc_conv1d_set_weight would create.
+extern "C" int32_t ttsc_conv1d_plan(const ttsc_conv1d* c, int32_t B, int64_t Lin, const ttsc_conv1d_epilogue* ep, int32_t phase, int32_t* info) {
+    TTSC_REQUIRE(c && info, "ttsc_conv1d_plan: null argument");
+    TTSC_REQUIRE(B > 0 && Lin > 0, "ttsc_conv1d_forward: bad B/Lin (%d, %lld)", B, (long long)Lin);
+    const int64_t Lout = ttsc_conv1d_out_len(c, Lin);
+    TTSC_REQUIRE(Lout > 0, "ttsc_conv1d_forward: output length %lld <= 0", (long long)Lout);
+    TTSC_REQUIRE(Lin < (1ll << 30) && Lout < (1ll << 30), "ttsc_conv1d_forward: length too large");
+    const std::vector<ConvPhaseGeom> geom = conv_phases(c->cfg, c->vfused);   // (what set_weight uploads, or will)
+    TTSC_REQUIRE(phase >= 0 && phase < (int)geom.size(), "ttsc_conv1d_plan: the layer has %d phase(s), asked for phase %d", (int)geom.size(), phase);
+    ConvPlan p;
+    if (!conv_plan(conv_layer_of(c), geom[phase], conv_launch_of(B, Lin, Lout, ep), conv_switches(), p)) {
+        set_error("%s", p.error);
+        return TTSC_EINVAL;
+    }
+    const int32_t out[10] = {p.rows, p.cols, p.tap_bucket, (int32_t)p.grid[0], (int32_t)p.grid[1], (int32_t)p.grid[2], (int32_t)p.lds, p.lean, p.acc_init, p.short_from};
+    std::copy(out, out + 10, info);
+    return p.family;
+}
 
 // Fused  y = x + conv2(lrelu(conv1(lrelu(x))))  for 32-channel ResBlock1 pairs (see respair32_f16x3_kernel).
 extern "C" int ttsc_respair_supported(const ttsc_conv1d* c1, const ttsc_conv1d* c2) {

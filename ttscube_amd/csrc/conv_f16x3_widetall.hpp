@@ -1,7 +1,6 @@
 // The wide- and tall-tile split-precision convolution kernels (conv_f16x3_wide_kernel: the square ResBlock layers of the wide stages;
 // conv_f16x3_tall_kernel: the first two upsamplers), the tile pipeline both are built on, and their launchers.  Included by conv1d.hip only.
 #pragma once
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv_kernels.hpp"
@@ -551,15 +550,11 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_tall_kernel(ConvArgs a) {
 }
 
 template <int C, int K, int D, bool LEAN>
-static int launch_f16_wide_l(const ConvArgs& a0, int B, hipStream_t s) {
+static int launch_f16_wide_l(const ConvArgs& a, int B, hipStream_t s) {
     constexpr int NT = 256;
-    dim3 grid((unsigned)ceil_div(a0.Lout, NT), (unsigned)(C / 128), (unsigned)B);
-    ConvArgs a = a0;
-    // (a.acc_init — the operands as the accumulators' initial value, see the kernel — is decided by the caller for the LAYER, not per kernel: the
-    // general kernel evaluates the same layer with the same arithmetic when the machine-fill rule sends it there)
-    // deep-prefetched epilogue operands (bit-identical to the plain epilogue; TTSC_CONV_EPI_PREFETCH=0 restores the four-rows-at-a-time one)
-    static const int epi_env = getenv("TTSC_CONV_EPI_PREFETCH") ? atoi(getenv("TTSC_CONV_EPI_PREFETCH")) : 1;
-    a.epi_prefetch = (epi_env && !a.gate && a.out_act == TTSC_ACT_NONE && a.Cout == C && (size_t)B * C * a.Lout < (1ull << 32)) ? 1 : 0;   // (32-bit element offsets)
+    dim3 grid((unsigned)ceil_div(a.Lout, NT), (unsigned)(C / 128), (unsigned)B);
+    // (a.acc_init — the operands as the accumulators' initial value, see the kernel — and a.epi_prefetch are decided by conv_plan for the LAYER,
+    // not per kernel: the general kernel evaluates the same layer with the same arithmetic when the machine-fill rule sends it there)
     if (int rc = ensure_full_lds((const void*)conv_f16x3_wide_kernel<C, K, D, LEAN>)) return rc;   // once per (device, kernel)
     hipLaunchKernelGGL((conv_f16x3_wide_kernel<C, K, D, LEAN>), grid, dim3(256), (WidePipe<C, K, D, LEAN>::LDS_BYTES), s, a);
     return launch_checked("conv_f16x3_wide_kernel");
@@ -571,15 +566,10 @@ static int launch_f16_wide(const ConvArgs& a, int B, hipStream_t s) {
 }
 
 template <int CIN, int J, int MI, int NJ, bool LEAN>
-static int launch_f16_tall_l(const ConvArgs& a0, int B, hipStream_t s) {
+static int launch_f16_tall_l(const ConvArgs& a, int B, hipStream_t s) {
     constexpr int NT = 2 * NJ * 32, MT = 2 * MI * 32;
-    ConvArgs a = a0;
     dim3 grid((unsigned)ceil_div(a.q_cnt, NT), (unsigned)(a.CoutP / MT), (unsigned)B);
-    static const int swz_env = getenv("TTSC_TALL_SWIZZLE") ? atoi(getenv("TTSC_TALL_SWIZZLE")) : 1;
-    if (swz_env && grid.y > 1) {   // XCD-aware 1-D launch (see the kernel): the row tiles of a q tile on one XCD, back to back
-        a.swz_nx = (int)grid.x;
-        a.swz_ny = (int)grid.y;
-        a.fold_B = B;
+    if (a.swz_nx > 0) {   // XCD-aware 1-D launch (see the kernel; conv_plan set swz_nx = grid.x, swz_ny = grid.y, fold_B = B)
         const unsigned tiles = (unsigned)round_up((int64_t)grid.x * B, 8);
         grid = dim3(tiles * grid.y, 1, 1);
     }

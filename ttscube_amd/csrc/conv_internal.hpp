@@ -1,14 +1,11 @@
 // Internal layout of a conv layer handle, shared by conv1d.hip (single-layer launches) and resblock.hip (fused chains).
 #pragma once
 #include "common.hpp"
+#include "conv_plan.hpp"
 
-struct ConvPhase {
+struct ConvPhase : ttsc::ConvPhaseGeom {   // the geometry (conv_plan.hpp: a function of the configuration) + the packed weights
     float* wp_dev = nullptr;
     void* wph_dev = nullptr;  // f16x3 fragments
-    int ntaps = 0, tap_base = 0, tap_step = 0;
-    int out_stride = 1, out_off = 0;
-    int r = 0;  // phase index (transposed)
-    std::vector<int> taps;  // kernel taps (or tap indices when vfused) of this phase, in GEMM order
 };
 
 struct ttsc_conv1d {
