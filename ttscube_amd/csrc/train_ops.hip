@@ -128,7 +128,8 @@ struct AdamArgs {
 __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, const AdamArgs& a) {
     p *= a.decay;
     m = m + (g - m) * a.om_b1;                 // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * a.b2 + (g * g) * a.om_b2;          // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    v = v * a.b2 + (a.om_b2 * g) * g;          // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2): value * t1 * t2 in torch's order, so that
+                                               // g up to sqrt(FLT_MAX / (1 - beta2)) keeps v finite as it does there (g * g first: inf from 1.8e19 on)
     const float denom = sqrtf(v) * a.inv_bc2s + a.eps;
     p = p - a.step_size * (m / denom);
 }
