@@ -302,6 +302,12 @@ int ttsc_conv_wgrad_split_grouped(const float* p_dev, const float* q_dev, float*
 int ttsc_conv_wgrad_split_bias(const float* p_dev, const float* q_dev, float* g_dev, float* db_dev, int32_t N, int32_t A, int32_t B, int64_t LP, int64_t LQ,
                                int32_t J, int32_t base, int32_t step, float q_scale, float q_slope, float* amax_q_dev, float* amax_p_dev, int32_t measure,
                                void* ws_dev, size_t ws_bytes, void* stream);
+/* How ttsc_conv_wgrad_split(_bias) divides a shape, from the functions the launcher itself calls; no device is touched.  Returns TTSC_OK, < 0 (and
+ * ttsc_last_error) for what the launch would refuse, and fills info[9] = {64-position chunks per batch item, work items N * chunks, 128 x 64 tiles,
+ * CH = items per split, splits (grid x; the last split may own fewer than CH items, and a split's items may straddle batch items), taps per launch
+ * min(5, 64 / |step| + 1), launches, taps of the last launch, bias-gradient slices per row}.  tests/test_conv_train_plan_cpu.py restates the rule,
+ * and tests/test_conv_train_f64_gpu.py asks it before every weight-gradient case (a case names the CH and the tap groups it means to reach). */
+int32_t ttsc_conv_wgrad_split_plan(int32_t N, int32_t A, int32_t B, int64_t LP, int32_t J, int32_t step, int32_t* info);
 
 /* Split-precision convolution of the training step (csrc/conv_train.hip): forward and data gradient of a dense, stride-1, dilated Conv1d
  * of the generator [EXTERNAL hifigan/models.py; trained by cube/networks/cubegan.py:131-170] and of the MPD / MSD discriminators
@@ -324,6 +330,13 @@ int ttsc_conv_train(const float* x_dev, const float* w_dev, const float* bias_de
                     int32_t B, int32_t Cin, int32_t Cout, int32_t K, int64_t Lin, int32_t padding, int32_t dilation, int32_t groups, int32_t flip, float in_scale,
                     float in_slope, float out_scale, float gate_slope, float* amax_x_dev, float* amax_w_dev, int32_t measure, void* ws_dev, size_t ws_bytes,
                     void* stream);
+/* Which instantiation of conv_f16x3_kernel (folded) ttsc_conv_train / ttsc_conv_train_packed launch for a shape, from the function the launcher
+ * itself calls (under the process's TTSC_TRAIN_NT, if set); no device is touched.  Returns TTSC_OK, < 0 (and ttsc_last_error) for what the launch
+ * would refuse, and fills info[10] = {MI (row tile 32 MI), NJ (column tile 128 NJ: 2 when ceil(S B / 256) * (CoutP / MT) >= 512 and K <= 16), tap
+ * bucket (3 / 7 / 11 / 16 / 21 / 41), S = max(Lin + padding, Lout) columns per utterance, S B, grid x, grid y, dynamic LDS bytes, CinP, CoutP}.
+ * tests/test_conv_train_plan_cpu.py restates the rule, and tests/test_conv_train_f64_gpu.py asks it before every case (a case names its tile). */
+int32_t ttsc_conv_train_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t K, int64_t Lin, int32_t padding, int32_t dilation, int32_t groups,
+                             int32_t* info);
 
 /* The same convolution on weight fragments prepared by a weight bank (below): no weight reduction, no packing launch, no workspace.
  * wfrag_dev / amax_w_dev: the bank entry's `pack_fwd` (forward) or `pack_dgrad` (data gradient: pass the differentiated layer's Cout as Cin and

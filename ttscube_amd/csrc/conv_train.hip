@@ -112,14 +112,21 @@ int launch_amax2(const float* x, long nx, float* out_x, const float* w, long nw,
     return TTSC_OK;
 }
 
+// What conv_train_impl launches for a shape: the ONE place that picks the tile (conv_train_plan below); ttsc_conv_train_plan reports it.
+struct ConvTrainPlan {
+    int MT, MI, NJ, nt, tmax;    // row tile (32 MI rows), column tile nt = 128 NJ, tap bucket (TMAX of the instantiation)
+    int CinP, CoutP, cin_tile;
+    int64_t Lout, S, cols;       // S = columns per utterance of the folded GEMM, cols = S B
+    unsigned gx, gy;
+    int span;                    // staged window: nt + (K - 1) dilation positions
+    size_t lds;
+};
+
 template <int MI, int NJ, int TMAX>
-static int launch_fold_t(const ConvArgs& a, hipStream_t s) {
-    constexpr int NT = 4 * NJ * 32;
-    dim3 grid((unsigned)ceil_div((long)a.fold_S * a.fold_B, NT), (unsigned)(a.CoutP / (32 * MI)), 1u);
-    const size_t lds = (size_t)a.span_pad * 4 * 16 + (size_t)a.ntaps * MI * 2 * 64 * 16;
-    TTSC_REQUIRE(lds <= 160 * 1024, "ttsc_conv_train: LDS footprint %zu", lds);
+static int launch_fold_t(const ConvArgs& a, const ConvTrainPlan& p, hipStream_t s) {
+    TTSC_REQUIRE(p.lds <= 160 * 1024, "ttsc_conv_train: LDS footprint %zu", p.lds);
     if (int rc = ensure_full_lds((const void*)conv_f16x3_kernel<MI, NJ, TMAX, true>)) return rc;
-    hipLaunchKernelGGL((conv_f16x3_kernel<MI, NJ, TMAX, true>), grid, dim3(256), lds, s, a);
+    hipLaunchKernelGGL((conv_f16x3_kernel<MI, NJ, TMAX, true>), dim3(p.gx, p.gy, 1u), dim3(256), p.lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("conv_f16x3_kernel (folded) launch failed: %s", hipGetErrorString(e));
@@ -128,12 +135,14 @@ static int launch_fold_t(const ConvArgs& a, hipStream_t s) {
     return TTSC_OK;
 }
 template <int MI, int NJ>
-static int launch_fold(const ConvArgs& a, hipStream_t s) {
-    if (a.ntaps <= 3) return launch_fold_t<MI, NJ, 3>(a, s);
-    if (a.ntaps <= 7) return launch_fold_t<MI, NJ, 7>(a, s);
-    if (a.ntaps <= 11) return launch_fold_t<MI, NJ, 11>(a, s);
-    if (a.ntaps <= 16) return launch_fold_t<MI, NJ, 16>(a, s);
-    return launch_fold_t<MI, NJ, 21>(a, s);   // MSD's k = 41, stride 2 layers: 21 taps after the de-interleave
+static int launch_fold(const ConvArgs& a, const ConvTrainPlan& p, hipStream_t s) {
+    switch (p.tmax) {
+        case 3: return launch_fold_t<MI, NJ, 3>(a, p, s);
+        case 7: return launch_fold_t<MI, NJ, 7>(a, p, s);
+        case 11: return launch_fold_t<MI, NJ, 11>(a, p, s);
+        case 16: return launch_fold_t<MI, NJ, 16>(a, p, s);
+        default: return launch_fold_t<MI, NJ, 21>(a, p, s);   // MSD's k = 41, stride 2 layers: 21 taps after the de-interleave
+    }
 }
 
 }  // namespace ttsc
@@ -170,6 +179,58 @@ extern "C" size_t ttsc_conv_train_workspace_bytes(int32_t Cin, int32_t Cout, int
     return 256 + (size_t)K * round_up(cin_tile, 16) * round_up(Cout, mt) * 2 * sizeof(_Float16);
 }
 
+// The tile rule of conv_train_impl, free of any device state: row tile from train_mt, column tile 256 wide when that still gives every CU two
+// workgroups, else 128 (and 128 when 21+ taps of weights share the LDS), the tap bucket, the folded column count, the grid and the LDS bytes.
+// TTSC_TRAIN_NT (measurement switch, read once per process) forces the column tile of the layers with K <= 16.
+static int conv_train_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t K, int64_t Lin, int32_t padding, int32_t dilation, int32_t groups, ConvTrainPlan* p) {
+    TTSC_REQUIRE(ttsc_conv_train_supported(Cin, Cout, K, dilation, groups), "ttsc_conv_train: shape not supported (Cin %d, Cout %d, K %d, dilation %d, groups %d)",
+                 Cin, Cout, K, dilation, groups);
+    TTSC_REQUIRE(B > 0 && Lin > 0 && padding >= 0, "ttsc_conv_train: bad B / Lin / padding");
+    const int64_t Lout = Lin + 2 * (int64_t)padding - (int64_t)dilation * (K - 1);
+    TTSC_REQUIRE(Lout > 0, "ttsc_conv_train: output length %lld <= 0", (long long)Lout);
+    const int64_t S = std::max<int64_t>(Lin + padding, Lout);
+    TTSC_REQUIRE((int64_t)B * Cin * Lin < (1ll << 31) && (int64_t)B * Cout * Lout < (1ll << 31) && S * B < (1ll << 30), "ttsc_conv_train: tensor too large");
+    const int MT = train_mt(Cout, groups, K), MI = MT / 32;
+    const int cin_g = Cin / groups, cout_g = Cout / groups;
+    p->MT = MT;
+    p->MI = MI;
+    p->cin_tile = groups > 1 ? (MT > cout_g ? MT / cout_g : 1) * cin_g : Cin;
+    p->CinP = round_up(p->cin_tile, 16);
+    p->CoutP = round_up(Cout, MT);
+    p->Lout = Lout;
+    p->S = S;
+    p->cols = S * B;
+    const long wg256 = ceil_div(p->cols, 256) * (p->CoutP / MT);
+    static const int nt_env = getenv("TTSC_TRAIN_NT") ? atoi(getenv("TTSC_TRAIN_NT")) : 0;
+    p->nt = K > 16 ? 128 : (nt_env ? nt_env : (wg256 >= 512 ? 256 : 128));
+    p->NJ = p->nt == 256 ? 2 : 1;
+    p->tmax = K > 21 ? 41 : K <= 3 ? 3 : K <= 7 ? 7 : K <= 11 ? 11 : K <= 16 ? 16 : 21;
+    p->span = p->nt + (K - 1) * dilation;
+    p->gx = (unsigned)ceil_div(p->cols, 4 * p->NJ * 32);
+    p->gy = (unsigned)(p->CoutP / (32 * MI));
+    p->lds = (size_t)p->span * 4 * 16 + (size_t)K * MI * 2 * 64 * 16;
+    return TTSC_OK;
+}
+
+extern "C" int32_t ttsc_conv_train_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t K, int64_t Lin, int32_t padding, int32_t dilation, int32_t groups,
+                                        int32_t* info) {
+    TTSC_REQUIRE(info, "ttsc_conv_train_plan: null argument");
+    ConvTrainPlan p;
+    if (int rc = conv_train_plan(B, Cin, Cout, K, Lin, padding, dilation, groups, &p)) return rc;
+    TTSC_REQUIRE(p.lds <= 160 * 1024, "ttsc_conv_train: LDS footprint %zu", p.lds);
+    info[0] = p.MI;
+    info[1] = p.NJ;
+    info[2] = p.tmax;
+    info[3] = (int32_t)p.S;
+    info[4] = (int32_t)p.cols;
+    info[5] = (int32_t)p.gx;
+    info[6] = (int32_t)p.gy;
+    info[7] = (int32_t)p.lds;
+    info[8] = p.CinP;
+    info[9] = p.CoutP;
+    return TTSC_OK;
+}
+
 // `prepacked` != null: the weight fragments (and *amax_w) come from a weight bank (ttsc_wbank_prepare): no weight reduction, no packing launch,
 // no workspace; `measure` bit 2: the caller zeroed *amax_x (a pooled word) — no memset launch either
 static int conv_train_impl(const float* x, const float* w, const _Float16* prepacked, const float* bias, const float* resid, const float* gate, float* y,
@@ -177,14 +238,10 @@ static int conv_train_impl(const float* x, const float* w, const _Float16* prepa
                            float in_scale, float in_slope, float out_scale, float gate_slope, float* amax_x, float* amax_w, int32_t measure, void* ws,
                            size_t ws_bytes, void* stream, float* amax_y = nullptr) {
     TTSC_REQUIRE(x && (w || prepacked) && y && (ws || prepacked), "ttsc_conv_train: null argument");
-    TTSC_REQUIRE(ttsc_conv_train_supported(Cin, Cout, K, dilation, groups), "ttsc_conv_train: shape not supported (Cin %d, Cout %d, K %d, dilation %d, groups %d)",
-                 Cin, Cout, K, dilation, groups);
-    TTSC_REQUIRE(B > 0 && Lin > 0 && padding >= 0, "ttsc_conv_train: bad B / Lin / padding");
+    ConvTrainPlan pl;
+    if (int rc = conv_train_plan(B, Cin, Cout, K, Lin, padding, dilation, groups, &pl)) return rc;
     TTSC_REQUIRE(in_slope >= 0.f && in_slope <= 1.f && in_scale > 0.f, "ttsc_conv_train: in_slope must be in [0, 1], in_scale positive");
-    const int64_t Lout = Lin + 2 * (int64_t)padding - (int64_t)dilation * (K - 1);
-    TTSC_REQUIRE(Lout > 0, "ttsc_conv_train: output length %lld <= 0", (long long)Lout);
-    const int64_t S = std::max<int64_t>(Lin + padding, Lout);
-    TTSC_REQUIRE((int64_t)B * Cin * Lin < (1ll << 31) && (int64_t)B * Cout * Lout < (1ll << 31) && S * B < (1ll << 30), "ttsc_conv_train: tensor too large");
+    const int64_t Lout = pl.Lout, S = pl.S;
     TTSC_REQUIRE(prepacked || ws_bytes >= ttsc_conv_train_workspace_bytes(Cin, Cout, K, groups), "ttsc_conv_train: workspace too small");
     TTSC_REQUIRE(prepacked ? (((uintptr_t)prepacked & 15) == 0 && amax_x && amax_w) : (((uintptr_t)ws & 15) == 0),
                  "ttsc_conv_train: workspace / fragments must be 16-byte aligned (and a bank's launches carry both range words)");
@@ -196,10 +253,9 @@ static int conv_train_impl(const float* x, const float* w, const _Float16* prepa
     if (!amax_w) { amax_w = ws_words + 1; measure |= 2; }
     if (prepacked) measure &= ~2;
     const _Float16* wph = prepacked ? prepacked : reinterpret_cast<_Float16*>(reinterpret_cast<char*>(ws) + 256);
-    const int MT = train_mt(Cout, groups, K), MI = MT / 32;
+    const int MT = pl.MT, MI = pl.MI;
     const int cin_g = Cin / groups, cout_g = Cout / groups;
-    const int cin_tile = groups > 1 ? (MT > cout_g ? MT / cout_g : 1) * cin_g : Cin;
-    const int CinP = round_up(cin_tile, 16), CoutP = round_up(Cout, MT);
+    const int cin_tile = pl.cin_tile, CinP = pl.CinP, CoutP = pl.CoutP;
 
     if (int rc = launch_amax2((measure & 1) ? x : nullptr, (long)B * Cin * Lin, amax_x, (measure & 2) ? w : nullptr, (long)cin_g * Cout * K, amax_w, s,
                               (measure & 4) != 0))
@@ -260,20 +316,15 @@ static int conv_train_impl(const float* x, const float* w, const _Float16* prepa
     if (const char* ev = getenv("TTSC_CONV_DBG")) a.dbg = atoi(ev);   // (measurement build only: see TTSC_DBG in conv_kernels.hpp)
 #endif
     a.q_cnt = (int)(S * B);
-    // column tile: 256 wide when that still gives every CU two workgroups, else 128 (and 128 when 21+ taps of weights share the LDS)
-    const long cols = S * B;
-    const long wg256 = ceil_div(cols, 256) * (CoutP / MT);
-    static const int nt_env = getenv("TTSC_TRAIN_NT") ? atoi(getenv("TTSC_TRAIN_NT")) : 0;
-    const int nt = K > 16 ? 128 : (nt_env ? nt_env : (wg256 >= 512 ? 256 : 128));
-    a.span = nt + (K - 1) * dilation;
+    a.span = pl.span;
     a.span_pad = a.span;
     int rc;
     if (K > 21)
-        rc = launch_fold_t<1, 1, 41>(a, s);
+        rc = launch_fold_t<1, 1, 41>(a, pl, s);
     else if (MI == 2)
-        rc = nt == 256 ? launch_fold<2, 2>(a, s) : launch_fold<2, 1>(a, s);
+        rc = pl.nt == 256 ? launch_fold<2, 2>(a, pl, s) : launch_fold<2, 1>(a, pl, s);
     else
-        rc = nt == 256 ? launch_fold<1, 2>(a, s) : launch_fold<1, 1>(a, s);
+        rc = pl.nt == 256 ? launch_fold<1, 2>(a, pl, s) : launch_fold<1, 1>(a, pl, s);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -863,6 +863,31 @@ static int wgrad_bias_slices(int32_t A, int64_t LP) {
     return (int)(s < 1 ? 1 : s);
 }
 
+// taps per launch: five accumulator pairs, and a Q window of at most 64 extra positions
+static int wgrad_split_jt_max(int step) {
+    const int st = step < 0 ? -step : step;
+    return std::min(5, 64 / st + 1);
+}
+
+extern "C" int32_t ttsc_conv_wgrad_split_plan(int32_t N, int32_t A, int32_t Bc, int64_t LP, int32_t J, int32_t step, int32_t* info) {
+    TTSC_REQUIRE(info, "ttsc_conv_wgrad_split_plan: null argument");
+    TTSC_REQUIRE(N > 0 && LP > 0 && ttsc_conv_wgrad_split_supported(A, Bc, J, step), "ttsc_conv_wgrad_split: shape not supported (N=%d A=%d B=%d J=%d step=%d)",
+                 N, A, Bc, J, step);
+    int chunks, CH, items, splits;
+    wgrad_split_plan(N, A, Bc, LP, &chunks, &CH, &items, &splits);
+    const int jt_max = wgrad_split_jt_max(step);
+    info[0] = chunks;
+    info[1] = items;
+    info[2] = ((A + 127) / 128) * ((Bc + 63) / 64);
+    info[3] = CH;
+    info[4] = splits;
+    info[5] = jt_max;
+    info[6] = (J + jt_max - 1) / jt_max;             // launches: groups of jt_max taps ...
+    info[7] = J - (info[6] - 1) * jt_max;            // ... and the last one's taps
+    info[8] = wgrad_bias_slices(A, LP);
+    return TTSC_OK;
+}
+
 extern "C" size_t ttsc_conv_wgrad_split_workspace_bytes(int32_t N, int32_t A, int32_t Bc, int64_t LP, int32_t J) {
     if (N <= 0 || A <= 0 || Bc <= 0 || LP <= 0 || J <= 0) return 0;
     int chunks, CH, items, splits;
@@ -918,8 +943,7 @@ extern "C" int ttsc_conv_wgrad_split_bias(const float* p_dev, const float* q_dev
     a.bias_part = db_dev ? bias_part : nullptr;
     a.bias_S = bias_S;
     a.bias_y0 = ((A + 127) / 128) * ((Bc + 63) / 64);
-    const int st = step < 0 ? -step : step;
-    const int jt_max = std::min(5, 64 / st + 1);   // taps per launch: five accumulator pairs, and a Q window of at most 64 extra positions
+    const int jt_max = wgrad_split_jt_max(step);
     for (int j0 = 0; j0 < J;) {
         const int jt = std::min(jt_max, J - j0);
         a.j0 = j0;

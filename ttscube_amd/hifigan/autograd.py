@@ -331,6 +331,15 @@ class HipConvFn(torch.autograd.Function):
         return dx, dw, db, dr, None, None, None, None, None, None
 
 
+def backward_context(tc, x, w, in_scale, in_slope, has_b=True, has_r=False, needs_input_grad=(True, True, True, False)):
+    """What HipConvFn.forward leaves for HipConvFn.backward after a per-launch call on the exact-kernel route (no bank, no pooled range words), for
+    callers that run the backward pass of a layer on its own — e.g. a ConvTranspose1d geometry whose forward kernel refuses it.  It lives beside
+    forward on purpose: whatever forward starts to save belongs here too."""
+    import types
+    return types.SimpleNamespace(tc=tc, in_scale=float(in_scale), in_slope=float(in_slope), pack=None, amax=None, saved_tensors=(x.contiguous(), w.contiguous()),
+                                 has_b=has_b, has_r=has_r, needs_input_grad=tuple(needs_input_grad))
+
+
 def hip_conv(tc, x, w, b=None, resid=None, in_scale=1.0, in_slope=1.0):
     """w from WeightBank.weight(i) carries the prepared fragments (`_ttsc_pack`); any other weight tensor is prepared per launch"""
     pack = getattr(w, '_ttsc_pack', None)
